@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SpMV throughput of the MI355X hot path on the reference's benchmark matrices.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--npz FILE] [--quick]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--npz FILE] [--quick] [--dump-outputs DIR]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
           or simply `python bench.py --gpus N`: without a launcher's WORLD_SIZE in the environment the script starts its N ranks itself
           and fails loudly (a JSON error line, exit code 2) when the machine shows fewer than N GPUs.
@@ -27,6 +27,7 @@ committed copy of profiles/hbm_traffic.json beside it and as the fallback).
 Everything else a default run measures (the other BASELINE configurations, the reference's whole sweep sw/bm.sh in all numeric modes,
 MALL-cold round-robin legs, the strong-scaling prediction: bench_extras.py) goes to `bench_details.json` next to this file and, one row
 per matrix, to stderr.  `--config NAME` measures only that configuration; `--quick` skips the extras.
+`--dump-outputs DIR` (N = 1) writes the headline configuration's y, as the last timed step left it, to DIR/y.npy.
 
 N > 1, nothing named (the driver's series): `value` = the N = 1 workload carried to N GPUs the way the path shards -- WEAK scaling: every rank owns
 an ogbl-ppa-sized row slab (own seed) of a matrix N slabs tall and all of x (hisparse_amd/sharding.py), no collective inside the SpMV, K slab
@@ -53,6 +54,7 @@ IMPL_NAMES = ["fixed", "float_pob", "float_stall"]
 SPIN_UP_STEPS = 1000    # untimed, at least: the clocks have dropped during the CPU legs (oracle, formatting)
 LINE_LIMIT = 4000       # bytes of the final JSON line (the driver's tail holds 8000)
 DETAILS_FILE = os.path.join(ROOT, "bench_details.json")
+DUMP_LIMIT = 64 * 10 ** 6   # bytes written by --dump-outputs, in all (.npy headers included)
 
 
 def spin_up(eng, batch=200, max_batches=40):
@@ -179,8 +181,10 @@ def kernel_name(stats):
             else "spmv_light_kernel" if stats.get("light_kernel") else "spmv_rowblock_kernel")
 
 
-def measure_single(np, datasets, device, host, name, steps, warmup, device_id=0, npz=None, impl_override=None, cpu_seconds=0.0, rank=0, with_spmm=True):
-    """One configuration on one GPU: load, parity against the oracle, K timed steps, HIP-event kernel time."""
+def measure_single(np, datasets, device, host, name, steps, warmup, device_id=0, npz=None, impl_override=None, cpu_seconds=0.0, rank=0, with_spmm=True,
+                   keep_y=False):
+    """One configuration on one GPU: load, parity against the oracle, K timed steps, HIP-event kernel time.
+    keep_y: ctx["y_timed"] = the packed y as hs_read_result returns it right after the K timed steps (before any other launch)."""
     t0 = time.perf_counter()
     cfg, csr = datasets.load(name, path=npz)
     impl = host.impl_id(impl_override or cfg.impl)
@@ -223,6 +227,7 @@ def measure_single(np, datasets, device, host, name, steps, warmup, device_id=0,
     eng.run_batch(steps)
     eng.sync()
     elapsed = time.perf_counter() - t0
+    y_timed = eng.read_result() if keep_y else None      # what the last timed step left for the caller (the legs below launch other kernels)
     # K steps of a small matrix are over in 0.1-0.3 ms, of which the final synchronisation and the first launch's latency are 20-70 us:
     # where K steps took under 2 ms, the same loop over enough steps for ~5 ms is reported BESIDE it (never `value`)
     long_steps, ms_long = 0, None
@@ -335,7 +340,23 @@ def measure_single(np, datasets, device, host, name, steps, warmup, device_id=0,
         res["spmm_extension"] = spmm
     log(rank, f"{name}/{IMPL_NAMES[impl]}: step {ms*1e3:.1f} us = {value:.0f} GB/s = {value/HBM_PEAK_GBS*100:.1f} % whole step; kernel {kernel_ms*1e3:.1f} us = "
               f"{achieved/HBM_PEAK_GBS*100:.1f} %; event pairs {kernel_ms_pairs*1e3:.1f} us" + (f"; graph replay {ms_graph*1e3:.1f} us per step" if ms_graph else ""))
-    return res, dict(eng=eng, packets=packets, csr=csr, x=x, xw=xw, impl=impl, nnz=nnz, y_cpu=y_cpu, t_cpu=t_cpu, reps=reps, cfg=cfg)
+    return res, dict(eng=eng, packets=packets, csr=csr, x=x, xw=xw, impl=impl, nnz=nnz, y_cpu=y_cpu, t_cpu=t_cpu, reps=reps, cfg=cfg, y_timed=y_timed)
+
+
+def dump_outputs(np, host, out_dir, impl, y_words):
+    """--dump-outputs DIR: the y of the last timed step as DIR/y.npy -- float64 in fixed point (Q8.24 word / 2^24: exact), float32 in the
+    float modes -- padded rows included, as hs_read_result hands it to the caller.  Past DUMP_LIMIT bytes: a fixed sample of rows (seed 0),
+    their indices beside it in DIR/y_rows.npy."""
+    y = y_words.astype(np.float64) / float(1 << 24) if impl == host.IMPL_FIXED else y_words.view(np.float32)
+    arrays = {"y": y}
+    budget = DUMP_LIMIT - 4096      # room for the .npy headers
+    if y.nbytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(y.size, budget // (y.itemsize + 8), replace=False))
+        arrays = {"y": y[rows], "y_rows": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def short_parity(parity):
@@ -508,12 +529,19 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="use the torch.distributed path even for one GPU")
     ap.add_argument("--predict-scaling", action="store_true",
                     help="N = 1: time every row slab of the 2-, 4- and 8-way split of --config (default mouse_gene) on this GPU and print the predicted compute-only scaling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write the y of the last one (the headline configuration's) to DIR/y.npy -- float64 in fixed "
+                         "point (exact), float32 in the float modes; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus < 1:
         fail(f"--gpus {args.gpus}: need at least one")
+    if args.steps < 1 or args.warmup < 0:
+        fail(f"--steps {args.steps} --warmup {args.warmup}: need at least one timed step and no negative warm-up")
+    if args.dump_outputs and (args.gpus > 1 or args.force_dist or args.predict_scaling or args.config == "bm"):
+        fail("--dump-outputs writes the one-GPU headline configuration's y: not with --gpus N > 1, --force-dist, --predict-scaling or --config bm")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)             # no launcher: start the N ranks ourselves (never falls through to the 1-GPU line)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -562,7 +590,10 @@ def main():
         scaling = suite["strong_scaling_prediction"]
         table = [summary_row(r) for r in measured.values()]
     res, ctx = measure_single(np, datasets, device, host, headline, args.steps, args.warmup, npz=args.npz, impl_override=args.impl,
-                              cpu_seconds=0.0 if args.no_cpu_baseline else args.cpu_seconds, rank=rank)
+                              cpu_seconds=0.0 if args.no_cpu_baseline else args.cpu_seconds, rank=rank, keep_y=bool(args.dump_outputs))
+    if args.dump_outputs:
+        names = dump_outputs(np, host, args.dump_outputs, ctx["impl"], ctx.pop("y_timed"))
+        log(rank, f"{headline}: y of the last timed step written to {args.dump_outputs} ({', '.join(n + '.npy' for n in names)})")
     cpu_line, cpu_full = (None, None) if args.no_cpu_baseline else cpu_baseline_for(np, host, ctx, rank)
     if not args.quick and not args.npz:
         cold = bench_extras.mall_cold(np, datasets, device, host, ctx, args.steps, args.warmup, rank)

@@ -155,20 +155,19 @@ def test_default_single_gpu_run_fits_the_drivers_tail():
 
 
 @__import__("pytest").mark.gpu
-@__import__("pytest").mark.parametrize("n", [2, 8])
+@__import__("pytest").mark.parametrize("n", [2, 4])
 def test_n_rank_dry_run_on_one_gpu(n):
     """main_distributed with N processes sharing GPU 0 -- set_device, the HIP engine, stream binding,
     hs_bind_device_result, slab parity against the oracle, the gathered layout, the peer-store gather over IPC handles, the JSON line --
-    everything of `bench.py --gpus N` except RCCL (gloo, host-staged)."""
+    everything of `bench.py --gpus N` except RCCL (gloo, host-staged).  N stays at 4: with the test process itself, no more than 6
+    processes may hold one shared GPU open at a time."""
     args = ["--gpus", str(n), "--backend", "gloo", "--share-gpu", "--config", "mouse_gene", "--steps", "20", "--warmup", "5"]
     rc, line, text = _bench(args, timeout=1200)
-    if rc != 0:      # seen ONCE, on a fresh box with the page cache cold (8 processes starting the HIP runtime at once), never reproduced in
-        # 30 further runs: keep the evidence, try once more; a second failure fails the test
+    if rc != 0:      # keep the whole output as evidence; a failed run on a shared GPU is not started again
         out = os.path.join(ROOT, "gpurun_out")
         if os.path.isdir(out):
-            with open(os.path.join(out, f"dry_run_{n}_first_failure.txt"), "w") as f:
+            with open(os.path.join(out, f"dry_run_{n}_failure.txt"), "w") as f:
                 f.write(text)
-        rc, line, text = _bench(args, timeout=1200)
     assert rc == 0, "\n".join(l for l in text.splitlines() if "rank" in l.lower() or "error" in l.lower() or "Traceback" in l or l.startswith("  File"))[-6000:]
     assert line["n_gpus"] == n and "DRY RUN" in line["backend"] and line["gather"] == "final"
     assert line["parity_vs_oracle"].startswith("bit-exact")
@@ -198,3 +197,65 @@ def test_default_series_dry_run_on_one_gpu():
     assert b4["scaling"] == "strong" and b4["parity_vs_oracle"].startswith("bit-exact") and len(b4["per_rank"]) == 2
     last = [l for l in text.splitlines() if l.startswith("{")][-1]
     assert len(last) < 4000
+
+
+# ---- --dump-outputs: the y of the last timed step, for comparing two builds output for output ------------------------------------------------
+@__import__("pytest").mark.parametrize("args", [["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", "d"],
+                                                ["--config", "bm", "--dump-outputs", "d"], ["--predict-scaling", "--dump-outputs", "d"]])
+def test_requests_bench_cannot_honour_are_refused(args, tmp_path):
+    rc, line, text = _bench(args + (["--backend", "gloo"] if "--gpus" in args else []), {"HISPARSE_HIP_LIB": CPU_LIB})
+    assert rc == 2, text
+    assert line is not None and "error" in line and "value" not in line
+    assert not os.path.exists(os.path.join(ROOT, "d"))
+
+
+def test_dump_outputs_is_exact_in_fixed_point_and_samples_past_the_limit(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    from hisparse_amd import host
+    words = np.array([0, 1, 1 << 24, 0xFFFFFFFF, 3 << 23], dtype=np.uint32)
+    assert bench.dump_outputs(np, host, str(tmp_path / "a"), host.IMPL_FIXED, words) == ["y"]
+    y = np.load(tmp_path / "a" / "y.npy")
+    assert y.dtype == np.float64 and np.array_equal(y, [0.0, 2.0 ** -24, 1.0, 256.0 - 2.0 ** -24, 1.5])
+    f = np.array([1.5, -2.25, 0.0], dtype=np.float32)
+    bench.dump_outputs(np, host, str(tmp_path / "b"), host.impl_id("float_pob"), f.view(np.uint32))
+    yf = np.load(tmp_path / "b" / "y.npy")
+    assert yf.dtype == np.float32 and np.array_equal(yf, f)
+    # more rows than 64 MB of float64 holds: a fixed sample, its row indices beside it, the same on every call
+    big = np.arange(bench.DUMP_LIMIT // 8 + 1000, dtype=np.uint32)
+    for d in ("c", "d"):
+        assert bench.dump_outputs(np, host, str(tmp_path / d), host.IMPL_FIXED, big) == ["y", "y_rows"]
+    files = [tmp_path / d / n for d in ("c", "d") for n in ("y.npy", "y_rows.npy")]
+    assert sum(os.path.getsize(p) for p in files[:2]) <= bench.DUMP_LIMIT
+    ys, rows = np.load(files[0]), np.load(files[1])
+    assert np.array_equal(ys, rows / 2.0 ** 24) and np.array_equal(np.load(files[2]), ys) and np.array_equal(np.load(files[3]), rows)
+    assert rows.size == np.unique(rows).size and rows.max() < big.size
+
+
+@__import__("pytest").mark.gpu
+@__import__("pytest").mark.parametrize("name", ["ppa_small", "nn_small"])
+def test_dump_outputs_writes_the_y_of_the_timed_steps(name, tmp_path):
+    """--dump-outputs DIR: y of the last timed step as DIR/y.npy, against the oracle on the same seeded inputs (bench.measure_single's x);
+    the line carries the step count asked for and the milliseconds one timed step took."""
+    import numpy as np
+    from hisparse_amd import datasets, host
+    from oracle import oracle as orc
+    out = tmp_path / "out"
+    rc, line, text = _bench(["--gpus", "1", "--config", name, "--quick", "--no-cpu-baseline", "--steps", "30", "--warmup", "5", "--dump-outputs", str(out)])
+    assert rc == 0, text[-4000:]
+    assert line["steps"] == 30 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["y.npy"]
+    cfg, csr = datasets.load(name)
+    impl = host.impl_id(cfg.impl)
+    cp = host.format_matrix(csr, impl, skip_empty_rows=cfg.skip_empty_rows)
+    rng = np.random.default_rng(2024)
+    x = rng.uniform(0.0, 2.0, cp.num_cols).astype(np.float32) if impl == host.IMPL_FIXED else rng.normal(size=cp.num_cols).astype(np.float32)
+    want = orc.spmv(impl, [cp.channel_ptr(c)[0] for c in range(16)], host.pack_vector(impl, x), cp.num_rows, cp.num_cols, cp.num_row_partitions,
+                    cp.num_col_partitions, cp.ob_bank, cp.vb_bank)
+    y = np.load(out / "y.npy")
+    assert y.shape == (cp.num_rows,)
+    if impl == host.IMPL_FIXED:
+        assert y.dtype == np.float64 and np.array_equal(y, want / 2.0 ** 24)
+    else:
+        assert y.dtype == np.float32 and np.allclose(y, want.view(np.float32), rtol=1e-4, atol=1e-4)

@@ -20,17 +20,16 @@ RESULT_LINE = re.compile(r"^\{Preprocessing: (\S+) s \| SpMV: (\S+) ms \| (\S+) 
 
 def run(*args, timeout=180):
     """The driver as a process.  A run that HANGS (seen once in round 5: `--gpus 1 --sharded` sat in RCCL's communicator set-up on a fresh
-    box for 300 s; the same command passed on every other box before and after) is killed, noted under gpurun_out/ and tried ONCE more;
-    a second hang fails the test."""
+    box for 300 s) is killed, its command and output are kept as evidence, and the test fails: a hung run on a shared GPU is not started again."""
     cmd = [BENCHMARK, *map(str, args)]
     try:
         return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
     except subprocess.TimeoutExpired as e:
         out = os.path.join(ROOT, "gpurun_out")
         if os.path.isdir(out):
-            with open(os.path.join(out, "benchmark_cli_first_hang.txt"), "a") as f:
+            with open(os.path.join(out, "benchmark_cli_hang.txt"), "a") as f:
                 f.write(" ".join(cmd) + "\n" + ((e.output or b"").decode(errors="replace") if isinstance(e.output, bytes) else str(e.output)) + "\n")
-        return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+        raise
 
 
 def glibc_rand_mod2(n):

@@ -37,6 +37,19 @@ def stream_format(request, monkeypatch):
     return request.param
 
 
+def _assert_forced_plan(stats, cp, impl, nnz):
+    """the image the library built is the one the stream_format fixture forced (or its documented substitute)"""
+    sub_tiles = cp.num_col_partitions * max(1, -(-(8 * cp.vb_bank) // 8192))      # column partitions x sub-tiles of 8192 columns per partition
+    sliced = os.environ.get("HISPARSE_COL_SLICES", "1") not in ("", "1")      # a forced sliced plan is the row-block kernel's
+    assert stats["light_kernel"] == (1 if os.environ.get("HISPARSE_LIGHT") == "1" and sub_tiles <= 16 and nnz > 0 and not sliced else 0)
+    forced = os.environ["HISPARSE_STREAM_FORMAT"]
+    if forced == "owner" and impl == 0:
+        forced = "pairs"                 # the 8-byte OWNER form is float only (fixed point: OWNER24 with saturating 32-bit accumulators)
+    if forced != "bitmap" or cp.num_rows * ((cp.num_cols + 63) // 64) * 8 <= (1 << 30):    # a forced bitmap gives way above 1 GiB of masks
+        got_format = device.STREAM_FORMATS[stats["stream_format"]]
+        assert got_format == forced or (os.environ.get("HISPARSE_AUX_BITS") == "24" and got_format == forced + "24")
+
+
 def _run_case(impl, m, vb, ob, skip, seed):
     csr, cp = cases.formatted(m, impl, vb, ob, skip)
     x = cases.random_x(cp.num_cols, seed, impl)
@@ -54,15 +67,7 @@ def _run_case(impl, m, vb, ob, skip, seed):
     stats = eng.stats()
     eng.close()
     assert stats["nnz"] == m.nnz
-    sub_tiles = cp.num_col_partitions * max(1, -(-(8 * cp.vb_bank) // 8192))      # column partitions x sub-tiles of 8192 columns per partition
-    sliced = os.environ.get("HISPARSE_COL_SLICES", "1") not in ("", "1")      # a forced sliced plan is the row-block kernel's
-    assert stats["light_kernel"] == (1 if os.environ.get("HISPARSE_LIGHT") == "1" and sub_tiles <= 16 and m.nnz > 0 and not sliced else 0)
-    forced = os.environ["HISPARSE_STREAM_FORMAT"]
-    if forced == "owner" and impl == 0:
-        forced = "pairs"                 # the 8-byte OWNER form is float only (fixed point: OWNER24 with saturating 32-bit accumulators)
-    if forced != "bitmap" or cp.num_rows * ((cp.num_cols + 63) // 64) * 8 <= (1 << 30):    # a forced bitmap gives way above 1 GiB of masks
-        got_format = device.STREAM_FORMATS[stats["stream_format"]]
-        assert got_format == forced or (os.environ.get("HISPARSE_AUX_BITS") == "24" and got_format == forced + "24")
+    _assert_forced_plan(stats, cp, impl, m.nnz)
     if impl == 0:
         assert np.array_equal(got, want), f"fixed-point mismatch at {np.nonzero(got != want)[0][:8]}"
         assert np.array_equal(again, want)
@@ -419,36 +424,53 @@ def test_pagerank_iterations(impl, graph, slices, monkeypatch):
         assert cases.float_close(got_y, y) and cases.float_close(got_y2, y2)
 
 
-@pytest.mark.parametrize("name", ["ogbl_ppa", "transformer_50", "ogbn_products", "mouse_gene"])
-def test_full_size_exact_known_answer(name, stream_format, monkeypatch):
+@pytest.fixture(scope="module")
+def full_size_cases():
+    """BASELINE.json's configurations at full size with the exact-answer inputs, generated and formatted once for every stream format pass"""
+    made = {}
+    yield made
+    made.clear()
+
+
+def _full_size_case(made, name):
     # BASELINE.json's configurations at FULL size (stand-in generators of hisparse_amd/datasets.py), with inputs that make the
     # answer independent of summation order and rounding, so it must match an integer CSR product bit for bit in every
     # numeric mode: all matrix values 2^-10, x in {0, 1, 2, 3}  =>  y[r] = 2^-10 * (sum of the selected x), exact in Q8.24
     # (no product needs rounding, no row reaches 256) and in fp32 (every partial sum is a multiple of 2^-10 below 2^14).
-    if stream_format != "pairs":
-        pytest.skip("one pass over the big matrices, in the format the library picks by itself")
-    monkeypatch.delenv("HISPARSE_STREAM_FORMAT")
-    monkeypatch.delenv("HISPARSE_AUX_BITS", raising=False)
-    import scipy.sparse as sp
-    from hisparse_amd import datasets
-    cfg, csr = datasets.load(name)
-    impl = host.impl_id(cfg.impl)
-    csr.fill(2.0 ** -10)
-    ip, ix, _ = csr.arrays()
-    rows, cols = csr.num_rows, csr.num_cols
-    cp = host.format_matrix(csr, impl, skip_empty_rows=True)
-    x_int = np.random.default_rng(77).integers(0, 4, cp.num_cols).astype(np.int64)
-    pattern = sp.csr_matrix((np.ones(len(ix), dtype=np.int64), ix.astype(np.int64), ip.astype(np.int64)), shape=(rows, cols))
-    sums = pattern @ x_int[:cols]                                    # exact integers
-    assert sums.max() < (1 << 17)                                    # < 256 * 2^10 / ... : far from saturation and from 2^24
-    want = np.zeros(cp.num_rows, dtype=np.uint32)
-    if impl == 0:
-        want[:rows] = (sums << 14).astype(np.uint32)                 # 2^-10 * s in Q8.24 = s * 2^14 LSB
-    else:
-        want[:rows] = (sums.astype(np.float64) / 1024.0).astype(np.float32).view(np.uint32)
+    if name not in made:
+        import scipy.sparse as sp
+        from hisparse_amd import datasets
+        cfg, csr = datasets.load(name)
+        impl = host.impl_id(cfg.impl)
+        csr.fill(2.0 ** -10)
+        ip, ix, _ = csr.arrays()
+        rows, cols = csr.num_rows, csr.num_cols
+        cp = host.format_matrix(csr, impl, skip_empty_rows=True)
+        x_int = np.random.default_rng(77).integers(0, 4, cp.num_cols).astype(np.int64)
+        pattern = sp.csr_matrix((np.ones(len(ix), dtype=np.int64), ix.astype(np.int64), ip.astype(np.int64)), shape=(rows, cols))
+        sums = pattern @ x_int[:cols]                                    # exact integers
+        assert sums.max() < (1 << 17)                                    # < 256 * 2^10 / ... : far from saturation and from 2^24
+        want = np.zeros(cp.num_rows, dtype=np.uint32)
+        if impl == 0:
+            want[:rows] = (sums << 14).astype(np.uint32)                 # 2^-10 * s in Q8.24 = s * 2^14 LSB
+        else:
+            want[:rows] = (sums.astype(np.float64) / 1024.0).astype(np.float32).view(np.uint32)
+        made[name] = (impl, cp, host.pack_vector(impl, x_int.astype(np.float32)), want, len(ix))
+    return made[name]
+
+
+@pytest.mark.parametrize("name", ["ogbl_ppa", "transformer_50", "ogbn_products", "mouse_gene"])
+def test_full_size_exact_known_answer(name, stream_format, monkeypatch, full_size_cases):
+    """The exact known answer (_full_size_case) at full size: in the format the library picks by itself on the "pairs" pass, in the
+    format the stream_format fixture forces on every other pass -- whole run and the reference's partition-by-partition loop."""
+    chosen = stream_format == "pairs"
+    if chosen:
+        monkeypatch.delenv("HISPARSE_STREAM_FORMAT")
+        monkeypatch.delenv("HISPARSE_AUX_BITS", raising=False)
+    impl, cp, xw, want, nnz = _full_size_case(full_size_cases, name)
     eng = device.SpmvEngine(impl)
     eng.load_matrix(cp)
-    eng.load_vector(host.pack_vector(impl, x_int.astype(np.float32)))
+    eng.load_vector(xw)
     eng.run()
     got = eng.read_result()
     # the same through the reference's partition-by-partition launch sequence
@@ -457,7 +479,9 @@ def test_full_size_exact_known_answer(name, stream_format, monkeypatch):
     again = eng.read_result()
     stats = eng.stats()
     eng.close()
-    assert stats["nnz"] == len(ix)
+    assert stats["nnz"] == nnz
+    if not chosen:
+        _assert_forced_plan(stats, cp, impl, nnz)
     assert np.array_equal(got, want), f"{int((got != want).sum())} rows differ"
     assert np.array_equal(again, want)
 
@@ -465,12 +489,12 @@ def test_full_size_exact_known_answer(name, stream_format, monkeypatch):
 @pytest.mark.parametrize("impl", IMPLS)
 @pytest.mark.parametrize("rows,cols,density", [(512, 33288, 0.5), (40, 9000, 0.3), (3000, 2500, 0.2), (129, 2049, 0.9), (20000, 4096, 0.15)])
 def test_dense_rows_pick_bitmap(impl, rows, cols, density, stream_format, monkeypatch):
-    """Pruned-NN shaped matrices (sw/bm.sh:21-27) choose the BITMAP format unforced: whole-run, partition-by-partition and
-    repeated launches against the oracle."""
-    if stream_format != "pairs":
-        pytest.skip("format chosen by the library here; one pass")
-    monkeypatch.delenv("HISPARSE_STREAM_FORMAT")
-    monkeypatch.delenv("HISPARSE_AUX_BITS", raising=False)
+    """Pruned-NN shaped matrices (sw/bm.sh:21-27) choose the BITMAP format unforced (the "pairs" pass) and run in the format the
+    stream_format fixture forces (every other pass): whole-run, partition-by-partition and repeated launches against the oracle."""
+    chosen = stream_format == "pairs"
+    if chosen:
+        monkeypatch.delenv("HISPARSE_STREAM_FORMAT")
+        monkeypatch.delenv("HISPARSE_AUX_BITS", raising=False)
     m = cases.random_csr(rows, cols, density, 17, impl)
     if impl != 0:
         m.data *= np.float32(0.05)       # pruned-NN weights (datasets.py: N(0, 0.05)): the ORACLE's fp32 running sum of 16 K unit-sized
@@ -487,16 +511,19 @@ def test_dense_rows_pick_bitmap(impl, rows, cols, density, stream_format, monkey
         eng.load_vector(xw)
         st = eng.stats()
         assert st["nnz"] == m.nnz
-        # rows padded to 1024 (float_stall) can leave so many empty rows that their masks outweigh the saving: element streams then
-        expect_bitmap = cp.num_rows * ((cp.num_cols + 63) // 64) * 8 <= 2 * m.nnz
-        # round 6: a FIXED-point dense layer over ONE x sub-tile of >= 2^20 non-zeros is a one-slice DELTA image where the fitted costs say so
-        # (stream_tiles.cpp: sliced_delta_possible; 2048 x 8192 at 15 %: 6.7 us against 11.6 us as a BITMAP image)
-        if impl == 0 and (rows, cols) == (3000, 2500):
-            assert device.STREAM_FORMATS[st["stream_format"]] == "delta" and st["col_slices"] == 1
-            expect_bitmap = False
-        assert (device.STREAM_FORMATS[st["stream_format"]] == "bitmap") == expect_bitmap
-        if expect_bitmap:
-            assert st["stream_bytes"] < 0.8 * 8 * m.nnz + (1 << 20)
+        if not chosen:
+            _assert_forced_plan(st, cp, impl, m.nnz)
+        else:
+            # rows padded to 1024 (float_stall) can leave so many empty rows that their masks outweigh the saving: element streams then
+            expect_bitmap = cp.num_rows * ((cp.num_cols + 63) // 64) * 8 <= 2 * m.nnz
+            # round 6: a FIXED-point dense layer over ONE x sub-tile of >= 2^20 non-zeros is a one-slice DELTA image where the fitted costs say so
+            # (stream_tiles.cpp: sliced_delta_possible; 2048 x 8192 at 15 %: 6.7 us against 11.6 us as a BITMAP image)
+            if impl == 0 and (rows, cols) == (3000, 2500):
+                assert device.STREAM_FORMATS[st["stream_format"]] == "delta" and st["col_slices"] == 1
+                expect_bitmap = False
+            assert (device.STREAM_FORMATS[st["stream_format"]] == "bitmap") == expect_bitmap
+            if expect_bitmap:
+                assert st["stream_bytes"] < 0.8 * 8 * m.nnz + (1 << 20)
         results = []
         for _ in range(3):
             eng.run()
