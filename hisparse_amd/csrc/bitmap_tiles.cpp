@@ -417,6 +417,8 @@ bool build_bitmap_tiles(const Layout& L, const void* const channel[NUM_HBM_CHANN
         }
         out.d_image = gpu->release_image();
         out.mfma.d_words = gpu->release_mfma();
+        out.d_value_map = gpu->release_value_map();
+        out.d_value_map2 = gpu->release_value_map2();
         timer.lap("bitmap: device emit");
     }
 

@@ -11,7 +11,7 @@
 //   fixed: every product narrowed to Q8.24 with AP_RND / AP_SAT (spmv/libfpga/pe.h:64), summed in 64 bits, clamped once (pe.h:72;
 //          saturating adds of non-negative terms are order free);
 //   float: one fp32 multiply per product (pe-pob.h:63-65, pe-stall.h:52), summed in double in storage order, rounded to fp32 once.
-// Core entry points only (create / load_matrix / load_matrix_csr / load_vector / run / run_partition / sync / read_result / stats /
+// Core entry points only (create / load_matrix / load_matrix_csr / update_values / load_vector / run / run_partition / sync / read_result / stats /
 // time_runs / errors); the device-memory hooks and the extensions answer HS_ERR_UNSUPPORTED.
 #include "hisparse_hip.h"
 
@@ -35,6 +35,7 @@ struct hs_context {
     uint32_t num_rows = 0, num_cols = 0, row_parts = 0, col_parts = 0;
     std::vector<uint64_t> indptr;      // CSR of the padded matrix: absolute columns, value words
     std::vector<uint32_t> indices, words;
+    bool from_csr = false;             // loaded by hs_load_matrix_csr: `words` are in the caller's non-zero order (hs_update_values)
     std::vector<uint32_t> x, y;
     hs_stats stats{};
     std::string error;
@@ -148,6 +149,7 @@ int hs_load_matrix(hs_context* ctx, const void* const channel[HS_NUM_CHANNELS], 
     const auto t0 = std::chrono::steady_clock::now();
     using namespace hisparse::dev::detail;
     ctx->matrix_loaded = false;
+    ctx->from_csr = false;
     Layout L;
     L.g = &ctx->geom;
     L.num_rows = num_rows; L.num_cols = num_cols; L.row_parts = num_row_partitions; L.col_parts = num_col_partitions;
@@ -224,10 +226,25 @@ int hs_load_matrix_csr(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, co
         if (ctx->impl == HS_IMPL_FIXED) ctx->words[e] = hisparse::q8_24_raw_from_double(double(values[e]));     // csr_matrix_convert_from_float
         else std::memcpy(&ctx->words[e], &values[e], 4);
     }
+    ctx->from_csr = true;
     ctx->stats = hs_stats{};
     loaded(ctx, uint32_t(rows), uint32_t(cols), uint32_t((rows + g.logical_ob - 1) / g.logical_ob), uint32_t((cols + g.logical_vb - 1) / g.logical_vb), t0);
     if (padded_rows) *padded_rows = uint32_t(rows);
     if (padded_cols) *padded_cols = uint32_t(cols);
+    return HS_OK;
+}
+
+// the stored value words of a CSR-loaded matrix, replaced in place (this library keeps the CSR: no option, no map)
+int hs_update_values(hs_context* ctx, const float* values, uint64_t nnz) {
+    if (!ctx) return HS_ERR_BAD_ARG;
+    if (!ctx->matrix_loaded) return fail(ctx, HS_ERR_NOT_LOADED, "hs_load_matrix has not been called");
+    if (!values) return fail(ctx, HS_ERR_BAD_ARG, "null argument");
+    if (!ctx->from_csr) return fail(ctx, HS_ERR_UNSUPPORTED, "no value map: the matrix came from hs_load_matrix (CPSR)");
+    if (nnz != ctx->words.size()) return fail(ctx, HS_ERR_BAD_ARG, "nnz must equal the loaded CSR's indptr[num_rows] (" + std::to_string(ctx->words.size()) + ")");
+    for (uint64_t e = 0; e < nnz; ++e) {
+        if (ctx->impl == HS_IMPL_FIXED) ctx->words[e] = hisparse::q8_24_raw_from_double(double(values[e]));     // csr_matrix_convert_from_float
+        else std::memcpy(&ctx->words[e], &values[e], 4);
+    }
     return HS_OK;
 }
 
@@ -311,5 +328,6 @@ int hs_spmm_device(hs_context* ctx, const void*, uint64_t, void*, uint64_t, uint
 int hs_spmm(hs_context* ctx, const void*, uint32_t, uint32_t, void*, uint32_t) { HS_CPU_UNSUPPORTED(ctx); }
 int hs_debug_read_tiles(hs_context* ctx, void*, uint64_t, void*, void*) { HS_CPU_UNSUPPORTED(ctx); }
 int hs_debug_read_mfma_image(hs_context* ctx, void*, uint64_t, uint64_t*) { HS_CPU_UNSUPPORTED(ctx); }
+int hs_update_values_device(hs_context* ctx, const float*, uint64_t) { HS_CPU_UNSUPPORTED(ctx); }
 
 }  // extern "C"

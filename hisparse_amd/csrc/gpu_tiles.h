@@ -30,7 +30,12 @@ class GpuTiler {
   public:
     GpuTiler(const detail::Layout& layout, const void* const channel[NUM_HBM_CHANNELS], const uint64_t n_packets[NUM_HBM_CHANNELS], hipStream_t stream);
     // the source is a CSR matrix (hs_load_matrix_csr): rows come from indptr, the element passes run one thread per kCsrSegment
-    // consecutive non-zeros, value words are made on the device (csr_matrix_convert_from_float, sw/data_loader.h:76-84)
+    // consecutive non-zeros, value words are made on the device (csr_matrix_convert_from_float, sw/data_loader.h:76-84).
+    // csr.value_map (option value_map): the emit passes also record, per non-zero in CSR order, the 32-bit word index its value word
+    // takes in the image (and in the matrix-engine image): the VALUE MAP hs_update_values scatters new values through.  The element
+    // formats then sort the CSR index as the payload in place of the value word and gather the words after the sort: 4 bytes per
+    // non-zero more during the load (`src`, the sorted CSR indices), 4 (+ 4 with a matrix-engine image) kept with the image.
+    // Images of 16 GiB or more get no map (the word indices would not fit in 32 bits).
     GpuTiler(const detail::Layout& layout, const CsrView& csr, hipStream_t stream);
     ~GpuTiler();
     GpuTiler(const GpuTiler&) = delete;
@@ -93,6 +98,9 @@ class GpuTiler {
     bool sweep_emit(const std::vector<SweepBlock>& blocks, uint64_t image_bytes, uint64_t slack_bytes);
     // hands the device image over (hipFree by the new owner)
     uint8_t* release_image() { uint8_t* p = d_image_; d_image_ = nullptr; return p; }
+    // the value maps (csr.value_map; null when none was built): nnz words into the image / into the matrix-engine image
+    uint32_t* release_value_map() { uint32_t* p = d_map_; d_map_ = nullptr; return p; }
+    uint32_t* release_value_map2() { uint32_t* p = d_map2_; d_map2_ = nullptr; return p; }
 
   private:
     bool fail(const std::string& what);
@@ -100,6 +108,8 @@ class GpuTiler {
     bool upload_channels();
     bool upload_csr(std::vector<uint32_t>& row_nnz);
     bool decode_error(const char* pass);
+    bool gather_values();
+    bool alloc_map(uint32_t** map, uint64_t image_bytes);
 
     detail::Layout L_;
     Geometry geom_;
@@ -126,6 +136,10 @@ class GpuTiler {
     uint64_t* d_bridges_ = nullptr;        // DELTA: inclusive scan of the bridge slots in front of every element
     uint8_t* d_image_ = nullptr;
     uint8_t* d_mfma_ = nullptr;            // BITMAP, float modes: the matrix-engine image (stream_tiles.h: MfmaImage)
+    bool value_map_ = false;               // CSR source with csr.value_map: build the value maps
+    uint32_t* d_src_ = nullptr;            // value map, element formats: CSR index of every sorted element (beside d_vals_)
+    uint32_t* d_map_ = nullptr;            // value map: word index into the image of every non-zero, CSR order
+    uint32_t* d_map2_ = nullptr;           // value map: word index into the matrix-engine image
 };
 
 }  // namespace dev

@@ -6,6 +6,9 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
+
+#include "value_word.h"
 
 namespace hisparse {
 namespace dev {
@@ -204,15 +207,14 @@ __device__ __forceinline__ bool csr_segment(const uint32_t* __restrict__ indptr,
     return true;
 }
 
-// value word of a CSR float: csr_matrix_convert_from_float (sw/data_loader.h:76-84) = the float's bits, or the Q8.24 conversion of
-// include/hisparse/q8_24.h (negatives, zeros and NaN -> 0; round half up; saturate) -- all exact in double, so bit-identical to the host
-__device__ __forceinline__ uint32_t value_word(float v, bool fixed) {
-    if (!fixed) return __float_as_uint(v);
-    const double d = double(v);
-    if (!(d > 0.0)) return 0u;
-    const double scaled = floor(d * 16777216.0 + 0.5);
-    return scaled >= 4294967296.0 ? 0xffffffffu : uint32_t(scaled);
+// value word of a CSR float: value_word.h (csr_matrix_convert_from_float, sw/data_loader.h:76-84)
+
+// Value map (gpu_tiles.h): word index of a value word stored at `at` in an image that starts at `base`
+__device__ __forceinline__ uint32_t word_index(const void* at, const void* base) {
+    return uint32_t((static_cast<const uint8_t*>(at) - static_cast<const uint8_t*>(base)) / 4);
 }
+// images whose word indices fit 32 bits (0xffffffff stays the "no entry" fill of a map)
+constexpr uint64_t kMapMaxWords = 0xffffffffull;
 
 __global__ __launch_bounds__(256) void csr_count_tiles_kernel(const uint32_t* __restrict__ indptr, const uint32_t* __restrict__ indices, uint32_t num_rows,
                                                              uint64_t nnz, uint32_t num_cols, uint32_t logical_vb, const uint32_t* __restrict__ block_of_row,
@@ -237,6 +239,8 @@ __global__ __launch_bounds__(256) void csr_count_tiles_kernel(const uint32_t* __
     if (run) atomicAdd(cnt + cur, run);
 }
 
+// kMap (value map): the sort payload is the CSR index of the element; map_gather_kernel makes the value words after the sort
+template <bool kMap>
 __global__ __launch_bounds__(256) void csr_keys_kernel(const uint32_t* __restrict__ indptr, const uint32_t* __restrict__ indices, const float* __restrict__ values,
                                                       uint32_t num_rows, uint64_t nnz, uint32_t logical_vb, uint32_t fixed,
                                                       const uint32_t* __restrict__ block_of_row, const uint32_t* __restrict__ range_row0,
@@ -251,8 +255,18 @@ __global__ __launch_bounds__(256) void csr_keys_kernel(const uint32_t* __restric
         const uint64_t unit = unit_of[size_t(b) * tiles + cp * S + k];
         const uint64_t pos = uint64_t(c.row - range_row0[b]) * kSubTileCols + (local - k * sub_width);
         keys[c.e] = (unit << kPosBits) | pos;
-        vals[c.e] = value_word(values[c.e], fixed != 0);
+        vals[c.e] = kMap ? uint32_t(c.e) : value_word(values[c.e], fixed != 0);
     }
+}
+
+// value map: the sorted payload is every element's CSR index -- keep it (src) and put the element's value word in its place
+__global__ __launch_bounds__(256) void map_gather_kernel(const float* __restrict__ values, uint32_t fixed, uint64_t n, uint32_t* __restrict__ vals,
+                                                        uint32_t* __restrict__ src) {
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t e = uint32_t(min<uint64_t>(vals[i], n - 1));      // (every payload is an index < n; the clamp keeps a failed pass in bounds)
+    src[i] = e;
+    vals[i] = value_word(values[e], fixed != 0);
 }
 
 __global__ __launch_bounds__(256) void duplicates_kernel(const uint64_t* __restrict__ keys, uint64_t n, uint32_t* flag) {
@@ -325,9 +339,11 @@ __device__ __forceinline__ void put(uint8_t* chunk, uint32_t lane, uint32_t valu
 
 // One workgroup per unit.  PAIRS: slot (chunk c, lane l) holds sorted element l * chunks + c (dense-row blocks: element i in chunk i / 64,
 // lane i % 64), chunks dealt round-robin to the wavefronts.
-template <bool k24>
+// kMap (every emit kernel): map[src[element]] = word index of the element's value word
+template <bool k24, bool kMap>
 __global__ __launch_bounds__(256) void emit_pairs_kernel(const DevicePlan* __restrict__ plans, const uint64_t* __restrict__ keys,
-                                                        const uint32_t* __restrict__ vals, uint8_t* __restrict__ image) {
+                                                        const uint32_t* __restrict__ vals, uint8_t* __restrict__ image, const uint32_t* __restrict__ src,
+                                                        uint32_t* __restrict__ map) {
     const DevicePlan& p = plans[blockIdx.x];
     constexpr uint32_t kStride = (k24 ? kChunkBytes24 : kChunkBytes) * kConsumerWaves, kShift = k24 ? kOwnerColBits : 16u;
     const bool dense = p.flags & kBlockDenseRows;
@@ -342,6 +358,7 @@ __global__ __launch_bounds__(256) void emit_pairs_kernel(const DevicePlan* __res
         if (i < p.n) {
             const uint32_t pos = uint32_t(keys[p.start + i] & kPosMask);
             put<k24>(chunk, lane, vals[p.start + i], ((pos / kSubTileCols) << kShift) | (pos % kSubTileCols));
+            if (kMap) map[src[p.start + i]] = word_index(chunk, image) + (k24 ? lane : 2 * lane);
         } else {
             put<k24>(chunk, lane, 0u, p.nrows << kShift);
         }
@@ -351,9 +368,10 @@ __global__ __launch_bounds__(256) void emit_pairs_kernel(const DevicePlan* __res
 // OWNER: per wavefront share, slot (step s, lane l) holds element l * steps + s of the share; the position word IS the key's low bits.
 // k24 (OWNER24, stream_tiles.h): step S of the wavefront's stream is slot S % 4 of its record S / 4 -- value word at lane * 16 + 4 j,
 // 24-bit position word (row relative to the share's first row) at 1024 + lane * 12 + 3 j.
-template <bool k24>
+template <bool k24, bool kMap>
 __global__ __launch_bounds__(256) void emit_owner_kernel(const DevicePlan* __restrict__ plans, const uint64_t* __restrict__ keys,
-                                                        const uint32_t* __restrict__ vals, uint8_t* __restrict__ image) {
+                                                        const uint32_t* __restrict__ vals, uint8_t* __restrict__ image, const uint32_t* __restrict__ src,
+                                                        uint32_t* __restrict__ map) {
     const DevicePlan& p = plans[blockIdx.x];
     for (uint32_t w = 0; w < kConsumerWaves; ++w) {
         const uint32_t steps = p.run_len[w], n = p.own_begin[w + 1] - p.own_begin[w];
@@ -370,18 +388,21 @@ __global__ __launch_bounds__(256) void emit_owner_kernel(const DevicePlan* __res
                 const uint32_t j = S % kOwnerRecordSteps;
                 const uint32_t where = i < n ? uint32_t(keys[mine + i] & kPosMask) - (row_base << kOwnerColBits) : kOwnerSpareField << kOwnerColBits;
                 reinterpret_cast<uint32_t*>(rec)[l * kOwnerRecordSteps + j] = value;
+                if (kMap && i < n) map[src[mine + i]] = word_index(rec, image) + l * kOwnerRecordSteps + j;
                 uint8_t* a = rec + kOwnerRecordValueBytes + (l * kOwnerRecordSteps + j) * 3;
                 a[0] = uint8_t(where); a[1] = uint8_t(where >> 8); a[2] = uint8_t(where >> 16);
             } else {
                 reinterpret_cast<uint2*>(stream + uint64_t(S) * kChunkBytes)[l] =
                     make_uint2(value, i < n ? uint32_t(keys[mine + i] & kPosMask) : (p.nrows + w) << kOwnerColBits);
+                if (kMap && i < n) map[src[mine + i]] = word_index(stream + uint64_t(S) * kChunkBytes, image) + 2 * l;
             }
         }
     }
 }
 
 // DELTA: slot -> (gap, value, position after the slot).  S(i) = slot of element i inside its unit = i + bridges up to and including i's.
-struct Slot { uint32_t gap, val, after; };
+struct Slot { uint32_t gap, val, after; uint64_t e; };       // e: the element's sorted index, or kNoElement for a bridge
+constexpr uint64_t kNoElement = ~0ull;
 __device__ __forceinline__ Slot delta_slot(const DevicePlan& p, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                            const uint64_t* __restrict__ bridges, uint64_t si) {
     const uint64_t bbase = p.start ? bridges[p.start - 1] : 0;
@@ -400,17 +421,19 @@ __device__ __forceinline__ Slot delta_slot(const DevicePlan& p, const uint64_t* 
             const uint64_t b = bridges[p.start + i] - bridges[p.start + i - 1];
             d = uint32_t(pos - prev - b * kBridgeAdvance);
         }
-        return Slot{d, vals[p.start + i], pos};
+        return Slot{d, vals[p.start + i], pos, p.start + i};
     }
     const uint32_t prev = uint32_t(keys[p.start + i - 1] & kPosMask);       // i > 0: element 0 has no bridges
     const uint64_t s_prev = (i - 1) + (bridges[p.start + i - 1] - bbase);
     const uint64_t k = si - (s_prev + 1);                                    // 0-based bridge in front of element i
-    return Slot{kBridgeGap, 0u, uint32_t(prev + (k + 1) * kBridgeAdvance)};
+    return Slot{kBridgeGap, 0u, uint32_t(prev + (k + 1) * kBridgeAdvance), kNoElement};
 }
 
+template <bool kMap>
 __global__ __launch_bounds__(256) void emit_delta_kernel(const DevicePlan* __restrict__ plans, const uint64_t* __restrict__ keys,
                                                         const uint32_t* __restrict__ vals, const uint64_t* __restrict__ bridges,
-                                                        uint8_t* __restrict__ image, uint32_t pad_gap) {
+                                                        uint8_t* __restrict__ image, uint32_t pad_gap, const uint32_t* __restrict__ src,
+                                                        uint32_t* __restrict__ map) {
     const DevicePlan& p = plans[blockIdx.x];
     if (!p.n) return;
     const uint32_t scratch_pos = p.nrows * kSubTileCols;      // local row nrows = the spare accumulator
@@ -435,7 +458,12 @@ __global__ __launch_bounds__(256) void emit_delta_kernel(const DevicePlan* __res
             if (j > run) { *gap_word = uint16_t(pad_gap); continue; }                            // the dead slot of an odd run
             const uint64_t si = s0 + (j - 1);
             uint32_t value = 0, gap = pad_gap;
-            if (si < p.slots) { const Slot s = delta_slot(p, keys, vals, bridges, si); value = s.val; gap = s.gap; }
+            if (si < p.slots) {
+                const Slot s = delta_slot(p, keys, vals, bridges, si);
+                value = s.val;
+                gap = s.gap;
+                if (kMap && s.e != kNoElement) map[src[s.e]] = word_index(value_word, image);      // (bridges carry no value)
+            }
             *value_word = value;
             *gap_word = uint16_t(gap);
         }
@@ -456,7 +484,8 @@ struct ElementSource {          // either the uploaded CPSR image or the CSR arr
     uint32_t num_groups, total_slots, num_rows, num_cols, logical_vb, fixed, csr;
 };
 
-// visit(row, absolute column, value word) for the elements thread t is responsible for; false + *err on a column outside the matrix
+// visit(row, absolute column, value word) for the elements thread t is responsible for; false + *err on a column outside the matrix.
+// A visit that takes a fourth argument also gets the element's CSR index (the value map; CSR sources only)
 template <typename Visit>
 __device__ __forceinline__ void visit_elements(const ElementSource& src, uint64_t t, uint32_t* err, Visit visit) {
     if (src.csr) {
@@ -466,7 +495,8 @@ __device__ __forceinline__ void visit_elements(const ElementSource& src, uint64_
             while (c.e >= src.indptr[c.row + 1]) ++c.row;
             const uint32_t col = src.indices[c.e];
             if (col >= src.num_cols) { report(err, kErrColumn, c.row / PACK_SIZE, c.row % PACK_SIZE); return; }
-            visit(c.row, col, value_word(src.values[c.e], src.fixed != 0));
+            if constexpr (std::is_invocable_v<Visit, uint32_t, uint32_t, uint32_t, uint64_t>) visit(c.row, col, value_word(src.values[c.e], src.fixed != 0), c.e);
+            else visit(c.row, col, value_word(src.values[c.e], src.fixed != 0));
         }
         return;
     }
@@ -474,7 +504,10 @@ __device__ __forceinline__ void visit_elements(const ElementSource& src, uint64_
     if (t >= src.total_slots || !find_segment(src.channels, src.groups, src.num_groups, src.total_slots, uint32_t(t), s)) return;
     const StreamGroup& g = src.groups[s.group];
     const uint32_t col_base = g.cp * src.logical_vb;
-    walk_segment(g, s, src.advance, [&](uint32_t row, uint32_t col, uint32_t val) { visit(row, col_base + col, val); });
+    if constexpr (std::is_invocable_v<Visit, uint32_t, uint32_t, uint32_t, uint64_t>)
+        walk_segment(g, s, src.advance, [&](uint32_t row, uint32_t col, uint32_t val) { visit(row, col_base + col, val, ~0ull); });
+    else
+        walk_segment(g, s, src.advance, [&](uint32_t row, uint32_t col, uint32_t val) { visit(row, col_base + col, val); });
 }
 
 // part k of n items cut into `parts`: [k n / parts, (k + 1) n / parts) -- the cut bitmap_tiles.cpp uses for column slices and row pieces
@@ -542,19 +575,24 @@ __global__ __launch_bounds__(256) void bitmap_prefix_kernel(uint32_t num_rows, u
     }
 }
 
-// every element's value word goes to (values before its row) + (values of its row in front of its group) + (set bits below its own)
+// every element's value word goes to (values before its row) + (values of its row in front of its group) + (set bits below its own).
+// kMap: map[CSR index] = that word index
+template <bool kMap>
 __global__ __launch_bounds__(256) void bitmap_values_kernel(ElementSource src, uint32_t slices, uint32_t GR, const uint32_t* __restrict__ range_of_row,
                                                            const GpuTiler::BitmapBlock* __restrict__ blocks, const uint64_t* __restrict__ row_value_base,
-                                                           const uint32_t* __restrict__ prefix, uint8_t* __restrict__ image, uint32_t* err) {
+                                                           const uint32_t* __restrict__ prefix, uint8_t* __restrict__ image, uint32_t* err,
+                                                           uint32_t* __restrict__ map) {
     const unsigned long long* image64 = reinterpret_cast<const unsigned long long*>(image);
     uint32_t* image32 = reinterpret_cast<uint32_t*>(image);
-    visit_elements(src, uint64_t(blockIdx.x) * blockDim.x + threadIdx.x, err, [&](uint32_t row, uint32_t col, uint32_t val) {
+    visit_elements(src, uint64_t(blockIdx.x) * blockDim.x + threadIdx.x, err, [&](uint32_t row, uint32_t col, uint32_t val, uint64_t e) {
         const uint32_t G = col / kBitmapGroupCols, k = slices > 1 ? part_of(GR, slices, G) : 0u;
         const GpuTiler::BitmapBlock& b = blocks[size_t(range_of_row[row]) * slices + k];
         const uint64_t in_block = uint64_t(row - b.row0) * b.stride + mask_offset(b, G - b.gs0);
         const unsigned long long m = image64[b.mask_word0 + in_block];
         const uint32_t below = uint32_t(__popcll(m & ((1ull << (col % kBitmapGroupCols)) - 1ull)));
-        image32[row_value_base[size_t(row) * slices + k] + prefix[b.prefix0 + in_block] + below] = val;
+        const uint64_t at = row_value_base[size_t(row) * slices + k] + prefix[b.prefix0 + in_block] + below;
+        image32[at] = val;
+        if (kMap) map[e] = uint32_t(at);
     });
 }
 
@@ -584,10 +622,13 @@ __global__ __launch_bounds__(256) void mfma_unit_base_kernel(const uint32_t* __r
     const uint32_t tile = t / chunks, c = t % chunks;
     unit_base[t] = uint64_t(c) * chunk < GR ? group_pos[size_t(tile) * GR + c * chunk] : group_pos[size_t(tile + 1) * GR];
 }
-// values in the order the kernel's lanes take them: tile, group, column of the group, row of the tile (bitmap_tiles.cpp)
+// values in the order the kernel's lanes take them: tile, group, column of the group, row of the tile (bitmap_tiles.cpp).
+// kMap: map2[CSR index] = the word index in the whole second image (values_word = where `values` starts in it)
+template <bool kMap>
 __global__ __launch_bounds__(256) void mfma_values_kernel(ElementSource src, uint32_t GR, const unsigned long long* __restrict__ masks2,
-                                                         const uint32_t* __restrict__ group_pos, uint32_t* __restrict__ values, uint32_t* err) {
-    visit_elements(src, uint64_t(blockIdx.x) * blockDim.x + threadIdx.x, err, [&](uint32_t row, uint32_t col, uint32_t val) {
+                                                         const uint32_t* __restrict__ group_pos, uint32_t* __restrict__ values, uint32_t* err,
+                                                         uint64_t values_word, uint32_t* __restrict__ map2) {
+    visit_elements(src, uint64_t(blockIdx.x) * blockDim.x + threadIdx.x, err, [&](uint32_t row, uint32_t col, uint32_t val, uint64_t e) {
         const uint32_t G = col / kBitmapGroupCols, p = col % kBitmapGroupCols, i = row % kMfmaTileRows;
         const uint64_t tg = uint64_t(row / kMfmaTileRows) * GR + G;
         const unsigned long long* m = masks2 + tg * kMfmaTileRows;
@@ -597,6 +638,7 @@ __global__ __launch_bounds__(256) void mfma_values_kernel(ElementSource src, uin
             if (r < i) rank += uint32_t((m[r] >> p) & 1ull);
         }
         values[group_pos[tg] + rank] = val;
+        if (kMap) map2[e] = uint32_t(values_word + group_pos[tg] + rank);
     });
 }
 
@@ -621,7 +663,7 @@ GpuTiler::GpuTiler(const Layout& layout, const void* const channel[NUM_HBM_CHANN
 }
 
 GpuTiler::GpuTiler(const Layout& layout, const CsrView& csr, hipStream_t stream)
-    : L_(layout), geom_(*layout.g), channel_(nullptr), n_packets_(nullptr), stream_(stream), csr_(&csr) {
+    : L_(layout), geom_(*layout.g), channel_(nullptr), n_packets_(nullptr), stream_(stream), csr_(&csr), value_map_(csr.value_map) {
     L_.g = &geom_;
 }
 
@@ -630,7 +672,7 @@ GpuTiler::~GpuTiler() {
         if (p) (void)hipFree(p);
     for (void* p : {static_cast<void*>(d_channels_), d_groups_, static_cast<void*>(d_advance_), static_cast<void*>(d_base_), static_cast<void*>(d_scalar_),
                     static_cast<void*>(d_block_of_row_), static_cast<void*>(d_keys_), static_cast<void*>(d_vals_), static_cast<void*>(d_bridges_),
-                    static_cast<void*>(d_image_), static_cast<void*>(d_mfma_)})
+                    static_cast<void*>(d_image_), static_cast<void*>(d_mfma_), static_cast<void*>(d_src_), static_cast<void*>(d_map_), static_cast<void*>(d_map2_)})
         if (p) (void)hipFree(p);
 }
 
@@ -739,6 +781,20 @@ bool GpuTiler::upload_csr(std::vector<uint32_t>& row_nnz) {
     return ok && check(hipStreamSynchronize(stream_), "upload");      // `indptr` is a temporary
 }
 
+// value map: the sorted payload (d_vals_) holds CSR indices -- move them to d_src_ and make the value words from the CSR values
+bool GpuTiler::gather_values() {
+    if (!check(hipMalloc(reinterpret_cast<void**>(&d_src_), std::max<uint64_t>(total_, 1) * 4), "hipMalloc(value map sources)")) return false;
+    hipLaunchKernelGGL(map_gather_kernel, dim3(uint32_t((total_ + 255) / 256)), dim3(256), 0, stream_, d_values_, uint32_t(geom_.impl == IMPL_FIXED), total_, d_vals_, d_src_);
+    return check(hipGetLastError(), "map_gather_kernel");
+}
+
+// value map: a map of `total_` words, 0xffffffff (no entry) until the emit kernels fill it; false = the image is too large for one
+bool GpuTiler::alloc_map(uint32_t** map, uint64_t image_bytes) {
+    if (image_bytes / 4 >= kMapMaxWords) return true;
+    const size_t bytes = std::max<uint64_t>(total_, 1) * 4;
+    return check(hipMalloc(reinterpret_cast<void**>(map), bytes), "hipMalloc(value map)") && check(hipMemsetAsync(*map, 0xff, bytes, stream_), "hipMemset(value map)");
+}
+
 bool GpuTiler::count_rows(std::vector<uint32_t>& row_nnz, uint64_t& nnz) {
     detail::PhaseTimer timer;
     if (csr_) {
@@ -837,9 +893,9 @@ bool GpuTiler::sort_elements(const std::vector<uint32_t>& block_of_row, const st
               check(hipMalloc(reinterpret_cast<void**>(&d_vals_), n * 4), "hipMalloc(values)");
     if (ok && csr_ && total_) {
         const uint64_t threads = (total_ + kCsrSegment - 1) / kCsrSegment;
-        hipLaunchKernelGGL(csr_keys_kernel, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, d_indptr_, d_indices_, d_values_, L_.num_rows, total_,
-                           uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), d_block_of_row_, d_row0, d_unit_of, tiles, S, L_.sub_width, d_keys_in,
-                           d_vals_in);
+        hipLaunchKernelGGL(value_map_ ? csr_keys_kernel<true> : csr_keys_kernel<false>, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, d_indptr_,
+                           d_indices_, d_values_, L_.num_rows, total_, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), d_block_of_row_, d_row0,
+                           d_unit_of, tiles, S, L_.sub_width, d_keys_in, d_vals_in);
         ok = check(hipGetLastError(), "csr_keys_kernel");
     } else if (ok && total_slots_) {
         hipLaunchKernelGGL(keys_kernel, dim3((total_slots_ + 255) / 256), dim3(256), 0, stream_, d_channels_, static_cast<const StreamGroup*>(d_groups_),
@@ -855,6 +911,7 @@ bool GpuTiler::sort_elements(const std::vector<uint32_t>& block_of_row, const st
         ok = check(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys_in, d_keys_, d_vals_in, d_vals_, total_, 0, end_bit, stream_), "radix sort (size)") &&
              check(hipMalloc(&d_temp, std::max<size_t>(temp_bytes, 16)), "hipMalloc(sort)") &&
              check(hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, d_keys_in, d_keys_, d_vals_in, d_vals_, total_, 0, end_bit, stream_), "radix sort");
+        if (ok && value_map_) ok = gather_values();
         if (ok) {
             (void)hipMemsetAsync(d_scalar_ + 4, 0, 4, stream_);
             hipLaunchKernelGGL(duplicates_kernel, dim3(uint32_t((total_ + 255) / 256)), dim3(256), 0, stream_, d_keys_, total_, d_scalar_ + 4);
@@ -966,15 +1023,26 @@ bool GpuTiler::emit(StreamFormat format, uint64_t image_bytes, uint64_t slack_by
     const size_t bytes = std::max<uint64_t>(image_bytes + slack_bytes, 256);
     bool ok = check(hipMalloc(reinterpret_cast<void**>(&d_image_), bytes), "hipMalloc(image)") && check(hipMemsetAsync(d_image_, 0, bytes, stream_), "hipMemset(image)") &&
               check(upload(&d_plans, dp, stream_), "upload plans");
+    if (ok && d_src_) ok = alloc_map(&d_map_, image_bytes);
     const dim3 grid(uint32_t(plans.size())), block(256);
     if (ok && !plans.empty()) {
+        const bool m = d_map_ != nullptr;
         switch (format) {
-            case kFormatPairs: hipLaunchKernelGGL(emit_pairs_kernel<false>, grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_); break;
-            case kFormatPairs24: hipLaunchKernelGGL(emit_pairs_kernel<true>, grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_); break;
-            case kFormatOwner: hipLaunchKernelGGL(emit_owner_kernel<false>, grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_); break;
-            case kFormatOwner24: hipLaunchKernelGGL(emit_owner_kernel<true>, grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_); break;
+            case kFormatPairs:
+                hipLaunchKernelGGL((m ? emit_pairs_kernel<false, true> : emit_pairs_kernel<false, false>), grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_, d_src_, d_map_);
+                break;
+            case kFormatPairs24:
+                hipLaunchKernelGGL((m ? emit_pairs_kernel<true, true> : emit_pairs_kernel<true, false>), grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_, d_src_, d_map_);
+                break;
+            case kFormatOwner:
+                hipLaunchKernelGGL((m ? emit_owner_kernel<false, true> : emit_owner_kernel<false, false>), grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_, d_src_, d_map_);
+                break;
+            case kFormatOwner24:
+                hipLaunchKernelGGL((m ? emit_owner_kernel<true, true> : emit_owner_kernel<true, false>), grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_, d_src_, d_map_);
+                break;
             case kFormatDelta:
-                hipLaunchKernelGGL(emit_delta_kernel, grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_bridges_, d_image_, is_float ? kBridgeGap : 0u);
+                hipLaunchKernelGGL(m ? emit_delta_kernel<true> : emit_delta_kernel<false>, grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_bridges_, d_image_,
+                                   is_float ? kBridgeGap : 0u, d_src_, d_map_);
                 break;
             default: ok = fail("gpu re-tile: format not supported");
         }
@@ -982,7 +1050,7 @@ bool GpuTiler::emit(StreamFormat format, uint64_t image_bytes, uint64_t slack_by
     }
     ok = ok && check(hipStreamSynchronize(stream_), "emit");
     if (d_plans) (void)hipFree(d_plans);
-    for (void** p : {reinterpret_cast<void**>(&d_keys_), reinterpret_cast<void**>(&d_vals_), reinterpret_cast<void**>(&d_bridges_)})
+    for (void** p : {reinterpret_cast<void**>(&d_keys_), reinterpret_cast<void**>(&d_vals_), reinterpret_cast<void**>(&d_bridges_), reinterpret_cast<void**>(&d_src_)})
         if (*p) { (void)hipFree(*p); *p = nullptr; }
     return ok;
 }
@@ -1055,6 +1123,10 @@ bool GpuTiler::bitmap_emit(uint32_t slices, uint32_t GR, const std::vector<uint3
     if (ok && errw[0]) ok = fail("CSR row " + std::to_string(uint64_t(errw[1]) * PACK_SIZE + errw[2]) + ": column index outside the matrix");
     timer.lap("gpu: bitmap masks");
     duplicates = ok && flags[0] != 0;
+    // value map: one for the image and one for the second image, or none (either too large for 32-bit word indices)
+    if (ok && !duplicates && value_map_ && image_bytes / 4 < kMapMaxWords && !(mfma && mfma->words_bytes / 4 >= kMapMaxWords)) {
+        ok = alloc_map(&d_map_, image_bytes) && (!mfma || alloc_map(&d_map2_, mfma->words_bytes));
+    }
     if (ok && !duplicates) {
         const uint64_t waves = uint64_t(L_.num_rows) * slices;
         if (waves) {
@@ -1062,7 +1134,8 @@ bool GpuTiler::bitmap_emit(uint32_t slices, uint32_t GR, const std::vector<uint3
             ok = check(hipGetLastError(), "bitmap_prefix_kernel");
         }
         if (ok && threads) {
-            hipLaunchKernelGGL(bitmap_values_kernel, egrid, block, 0, stream_, src, slices, GR, d_range, d_blocks, d_row_base, d_prefix, d_image_, d_scalar_);
+            hipLaunchKernelGGL(d_map_ ? bitmap_values_kernel<true> : bitmap_values_kernel<false>, egrid, block, 0, stream_, src, slices, GR, d_range, d_blocks,
+                               d_row_base, d_prefix, d_image_, d_scalar_, d_map_);
             ok = check(hipGetLastError(), "bitmap_values_kernel");
         }
         if (ok && num_runs) {
@@ -1089,7 +1162,8 @@ bool GpuTiler::bitmap_emit(uint32_t slices, uint32_t GR, const std::vector<uint3
                 ok = check(hipGetLastError(), "mfma_unit_base_kernel");
             }
             if (ok && threads) {
-                hipLaunchKernelGGL(mfma_values_kernel, egrid, block, 0, stream_, src, mfma->groups, masks2, d_pos, words + mfma->values_word, d_scalar_);
+                hipLaunchKernelGGL(d_map2_ ? mfma_values_kernel<true> : mfma_values_kernel<false>, egrid, block, 0, stream_, src, mfma->groups, masks2, d_pos,
+                                   words + mfma->values_word, d_scalar_, uint64_t(mfma->values_word), d_map2_);
                 ok = check(hipGetLastError(), "mfma_values_kernel");
             }
         }
@@ -1102,6 +1176,8 @@ bool GpuTiler::bitmap_emit(uint32_t slices, uint32_t GR, const std::vector<uint3
     if (!ok || duplicates) {
         if (d_image_) { (void)hipFree(d_image_); d_image_ = nullptr; }
         if (d_mfma_) { (void)hipFree(d_mfma_); d_mfma_ = nullptr; }
+        if (d_map_) { (void)hipFree(d_map_); d_map_ = nullptr; }
+        if (d_map2_) { (void)hipFree(d_map2_); d_map2_ = nullptr; }
     }
     return ok;
 }
@@ -1117,16 +1193,18 @@ __global__ __launch_bounds__(256) void sweep_lines_kernel(ElementSource src, uin
 
 // (the order the elements arrive in does not matter: the sort key is the element's complete identity -- two equal keys are a duplicate entry,
 // which the host builder takes)
+// kMap: the payload is the element's CSR index (map_gather_kernel makes the value words after the sort)
+template <bool kMap>
 __global__ __launch_bounds__(256) void sweep_keys_kernel(ElementSource src, const uint32_t* __restrict__ range_of_row, const uint32_t* __restrict__ range_row0,
                                                         SweepSlices slices, unsigned long long* cursor, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                         uint32_t* err) {
-    visit_elements(src, uint64_t(blockIdx.x) * blockDim.x + threadIdx.x, err, [&](uint32_t row, uint32_t col, uint32_t val) {
+    visit_elements(src, uint64_t(blockIdx.x) * blockDim.x + threadIdx.x, err, [&](uint32_t row, uint32_t col, uint32_t val, uint64_t e) {
         const uint32_t range = range_of_row[row];
         uint32_t k = 0;
         while (k + 1 < slices.n && col >= slices.col[k + 1]) ++k;
         const uint64_t at = atomicAdd(cursor, 1ull);
         keys[at] = (uint64_t(range) * slices.n + k) << 48 | uint64_t(col) << 16 | (row - range_row0[range]);
-        vals[at] = val;
+        vals[at] = kMap ? uint32_t(e) : val;
     });
 }
 
@@ -1146,8 +1224,10 @@ __global__ __launch_bounds__(256) void sweep_spans_kernel(const uint64_t* __rest
 }
 
 // one thread per element slot of the image: chunk c of all blocks' chunks, lane l
+template <bool kMap>
 __global__ __launch_bounds__(256) void sweep_emit_kernel(const GpuTiler::SweepBlock* __restrict__ blocks, uint32_t num_blocks, uint64_t total_chunks,
-                                                        const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint8_t* __restrict__ image) {
+                                                        const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint8_t* __restrict__ image,
+                                                        const uint32_t* __restrict__ src, uint32_t* __restrict__ map) {
     const uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x, c = t / kWaveLanes;
     const uint32_t lane = uint32_t(t % kWaveLanes);
     if (c >= total_chunks) return;
@@ -1165,6 +1245,7 @@ __global__ __launch_bounds__(256) void sweep_emit_kernel(const GpuTiler::SweepBl
         const uint64_t key = keys[b.first + first + lane];
         slot[0] = vals[b.first + first + lane];
         slot[1] = uint32_t(key & 0xffffu) << 16 | (uint32_t(key >> 16) - base);
+        if (kMap) map[src[b.first + first + lane]] = word_index(slot, image);
     } else {
         slot[0] = 0u;
         slot[1] = b.nrows << 16;
@@ -1218,7 +1299,8 @@ bool GpuTiler::sweep_sort(const std::vector<uint32_t>& range_of_row, const std::
               check(hipMalloc(reinterpret_cast<void**>(&d_start), (size_t(num_blocks) + 1) * 8), "hipMalloc(block starts)") &&
               check(hipMemsetAsync(d_start, 0xff, (size_t(num_blocks) + 1) * 8, stream_), "hipMemset");
     if (ok && threads) {
-        hipLaunchKernelGGL(sweep_keys_kernel, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, src, d_range, d_row0, sl, d_cursor, d_keys_in, d_vals_in, d_scalar_);
+        hipLaunchKernelGGL(value_map_ ? sweep_keys_kernel<true> : sweep_keys_kernel<false>, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, src, d_range,
+                           d_row0, sl, d_cursor, d_keys_in, d_vals_in, d_scalar_);
         ok = check(hipGetLastError(), "sweep_keys_kernel");
     }
     if (timer.on) { (void)hipStreamSynchronize(stream_); timer.lap("gpu: sweep keys"); }
@@ -1230,6 +1312,7 @@ bool GpuTiler::sweep_sort(const std::vector<uint32_t>& range_of_row, const std::
         ok = end_bit <= 64 && check(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys_in, d_keys_, d_vals_in, d_vals_, total_, 0, end_bit, stream_), "radix sort (size)") &&
              check(hipMalloc(&d_temp, std::max<size_t>(temp_bytes, 16)), "hipMalloc(sort)") &&
              check(hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, d_keys_in, d_keys_, d_vals_in, d_vals_, total_, 0, end_bit, stream_), "radix sort");
+        if (ok && value_map_) ok = gather_values();
         if (ok) {
             const dim3 grid(uint32_t((total_ + 255) / 256));
             hipLaunchKernelGGL(sweep_starts_kernel, grid, dim3(256), 0, stream_, d_keys_, total_, d_start, d_flags);
@@ -1264,15 +1347,18 @@ bool GpuTiler::sweep_emit(const std::vector<SweepBlock>& blocks, uint64_t image_
     SweepBlock* d_blocks = nullptr;
     bool ok = check(hipMalloc(reinterpret_cast<void**>(&d_image_), bytes), "hipMalloc(image)") && check(upload(&d_blocks, blocks, stream_), "upload blocks");
     if (ok && slack_bytes) ok = check(hipMemsetAsync(d_image_ + image_bytes, 0, slack_bytes, stream_), "hipMemset(slack)");
+    if (ok && d_src_) ok = alloc_map(&d_map_, image_bytes);
     if (ok && total_chunks) {
-        hipLaunchKernelGGL(sweep_emit_kernel, dim3(uint32_t((total_chunks * kWaveLanes + 255) / 256)), dim3(256), 0, stream_, d_blocks, uint32_t(blocks.size()), total_chunks,
-                           d_keys_, d_vals_, d_image_);
+        hipLaunchKernelGGL(d_map_ ? sweep_emit_kernel<true> : sweep_emit_kernel<false>, dim3(uint32_t((total_chunks * kWaveLanes + 255) / 256)), dim3(256), 0, stream_,
+                           d_blocks, uint32_t(blocks.size()), total_chunks, d_keys_, d_vals_, d_image_, d_src_, d_map_);
         ok = check(hipGetLastError(), "sweep_emit_kernel");
     }
     ok = ok && check(hipStreamSynchronize(stream_), "sweep emit");
     timer.lap("gpu: sweep emit");
     if (d_blocks) (void)hipFree(d_blocks);
+    if (d_src_) { (void)hipFree(d_src_); d_src_ = nullptr; }
     if (!ok && d_image_) { (void)hipFree(d_image_); d_image_ = nullptr; }
+    if (!ok && d_map_) { (void)hipFree(d_map_); d_map_ = nullptr; }
     return ok;
 }
 

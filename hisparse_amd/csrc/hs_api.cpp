@@ -91,6 +91,13 @@ struct hs_context {
     float* d_mfma_partial = nullptr;
     uint32_t* d_mfma_flag = nullptr;
     uint32_t mfma_call = 0;
+    // hs_update_values (option value_map, CSR loads built on the device): per non-zero in CSR order, the u32 word index of its value in
+    // d_image (and in d_mfma); a staging buffer for values handed in from the host (allocated on first use); why there is no map
+    uint32_t* d_value_map = nullptr;
+    uint32_t* d_value_map2 = nullptr;
+    uint64_t value_map_nnz = 0;
+    float* d_value_stage = nullptr;
+    std::string value_map_why = "no matrix has been loaded";
 
     // SpMSpV extension: the matrix once more, in CSC form (hs_load_matrix_csc), + scratch
     uint32_t* d_csc_indptr = nullptr;
@@ -150,6 +157,7 @@ const char* const kOptionKeys[] = {
     "STREAM_FORMAT", "COL_SLICES", "MAX_ROWS", "CROSS_PARTITIONS", "SPMM_VECTORS", "ROW_RUNS", "AUX_BITS", "XCD_AFFINITY", "STREAM_RESIDENT", "RETILE", "PLAN_DEBUG",
     "BITMAP_SKEW", "BITMAP_X_LDS", "BITMAP_BUILD", "WALK_LANES", "NO_MFMA_IMAGE", "MFMA_CHUNK", "LIGHT", "LIGHT_WGS", "SWEEP",
     "DELTA_DEAL", "POW2_SLICES", "SPMM_FUSED", "SPMM_MFMA", "SPMSPV", "SPMSPV_CROSSOVER", "ITERATE_GRAPH", "BATCH_GRAPH", "CARRY_COMBINE", "AUTOTUNE", "PLAN_CENSUS",
+    "VALUE_MAP",
 };
 
 void drop_batch_graph(hs_context* c) {
@@ -187,6 +195,12 @@ void free_matrix(hs_context* c) {
     c->d_mfma = c->d_mfma_x = c->d_mfma_flag = nullptr;
     c->d_mfma_partial = nullptr;
     c->mfma_info = hisparse::dev::MfmaImage();
+    for (void* p : {static_cast<void*>(c->d_value_map), static_cast<void*>(c->d_value_map2), static_cast<void*>(c->d_value_stage)})
+        if (p) (void)hipFree(p);
+    c->d_value_map = c->d_value_map2 = nullptr;
+    c->d_value_stage = nullptr;
+    c->value_map_nnz = 0;
+    c->value_map_why = "no matrix has been loaded";
     c->d_image = nullptr;
     c->d_blocks = nullptr;
     c->d_units = nullptr;
@@ -430,8 +444,15 @@ int hs_destroy(hs_context* ctx) {
 
 namespace {
 // hs_load_matrix (CPSR channel buffers) and hs_load_matrix_csr (`csr` != nullptr, channel / n_packets null) behind one body
-int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t* n_packets, const hisparse::dev::CsrView* csr,
-                     uint32_t num_rows, uint32_t num_cols, uint32_t num_row_partitions, uint32_t num_col_partitions) {
+// plan-time option value_map = 1: hs_load_matrix_csr keeps the value map of hs_update_values
+bool value_map_asked(const hs_context* c) {
+    const char* v = ctx_option(c, "HISPARSE_VALUE_MAP");
+    return v && std::atoi(v) != 0;
+}
+
+// want_map: build the value map of hs_update_values if the option asks for it (autotune's candidate loads do not)
+int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t* n_packets, const hisparse::dev::CsrView* csr_in,
+                     uint32_t num_rows, uint32_t num_cols, uint32_t num_row_partitions, uint32_t num_col_partitions, bool want_map) {
     const Geometry& g = ctx->geom;
     if (num_rows == 0 || num_cols == 0) return fail(ctx, HS_ERR_BAD_ARG, "empty matrix");
     if (num_rows % g.row_divisor != 0 || num_cols % hisparse::PACK_SIZE != 0)
@@ -444,14 +465,25 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
     HS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_matrix(ctx);
     const auto t0 = std::chrono::steady_clock::now();
+    const bool map_on = value_map_asked(ctx);
+    hisparse::dev::CsrView csr_view;
+    const hisparse::dev::CsrView* csr = nullptr;
+    if (csr_in) {
+        csr_view = *csr_in;
+        csr_view.value_map = map_on && want_map;
+        csr = &csr_view;
+    }
 
     hisparse::dev::StreamTiles tiles;
     std::string why;
     auto drop_device_images = [](hisparse::dev::StreamTiles& t) {      // what a builder left on the device for a load that fails after it
         if (t.d_image) (void)hipFree(t.d_image);
         if (t.mfma.d_words) (void)hipFree(t.mfma.d_words);
+        if (t.d_value_map) (void)hipFree(t.d_value_map);
+        if (t.d_value_map2) (void)hipFree(t.d_value_map2);
         t.d_image = nullptr;
         t.mfma.d_words = nullptr;
+        t.d_value_map = t.d_value_map2 = nullptr;
     };
     // The per-non-zero passes of the re-tiling run on the GPU (gpu_tiles.h) unless HISPARSE_RETILE=host; BITMAP images and matrices
     // with duplicate entries are built by the host code, which also remains the byte-for-byte checker of the GPU path.
@@ -520,8 +552,11 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
     if (tiles.d_image) { ctx->d_image = tiles.d_image; }
     if (tiles.mfma.d_words) { ctx->d_mfma = reinterpret_cast<uint32_t*>(tiles.mfma.d_words); }
     const bool image_on_device = tiles.d_image != nullptr, mfma_on_device = tiles.mfma.d_words != nullptr;
+    ctx->d_value_map = tiles.d_value_map;
+    ctx->d_value_map2 = tiles.d_value_map2;
     tiles.d_image = nullptr;
     tiles.mfma.d_words = nullptr;
+    tiles.d_value_map = tiles.d_value_map2 = nullptr;
     // the dynamic-LDS cap is a property of the FUNCTION, not of this context: always raise it to the full 160 KiB, so that a
     // second context with a smaller matrix on the same device cannot lower it under a first one's launches
     HS_HIP(ctx, hisparse::dev::configure_spmv_kernels(hisparse::dev::kMaxLdsBytes));
@@ -584,11 +619,27 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
             ctx->mfma_info.offsets_word = mi.offsets_word; ctx->mfma_info.values_word = mi.values_word;
         } else {
             (void)hipGetLastError();
-            for (void* p : {static_cast<void*>(ctx->d_mfma), static_cast<void*>(ctx->d_mfma_x), static_cast<void*>(ctx->d_mfma_partial), static_cast<void*>(ctx->d_mfma_flag)})
+            for (void* p : {static_cast<void*>(ctx->d_mfma), static_cast<void*>(ctx->d_mfma_x), static_cast<void*>(ctx->d_mfma_partial), static_cast<void*>(ctx->d_mfma_flag),
+                            static_cast<void*>(ctx->d_value_map2)})
                 if (p) (void)hipFree(p);
             ctx->d_mfma = ctx->d_mfma_x = ctx->d_mfma_flag = nullptr;
             ctx->d_mfma_partial = nullptr;
+            ctx->d_value_map2 = nullptr;      // (no second image: nothing for its map to point into)
         }
+    }
+    // the value map: kept, or why there is none (hs_update_values reports it)
+    if (ctx->d_value_map) {
+        ctx->value_map_nnz = tiles.nnz;
+        ctx->value_map_why.clear();
+    } else if (!map_on) {
+        ctx->value_map_why = "the value_map option was off when the matrix was loaded";
+    } else if (!csr) {
+        ctx->value_map_why = "the matrix came from hs_load_matrix (CPSR): only hs_load_matrix_csr keeps a value map";
+    } else if (!image_on_device) {
+        ctx->value_map_why = "the image was built by the host builder (duplicate (row, column) entries, bitmap_build=host, or SWEEP chunks spanning more than 65535 "
+                             "columns): it has no value map";
+    } else {
+        ctx->value_map_why = "the image is 16 GiB or larger: its word indices do not fit 32 bits";
     }
     if (debug) std::fprintf(stderr, "load: descriptors + result buffers on the device after %.1f ms\n", since());
     ctx->num_rows = num_rows;
@@ -676,16 +727,19 @@ double time_loaded_plan(hs_context* ctx, int runs) {
 
 int load_matrix_impl(hs_context* ctx, const void* const* channel, const uint64_t* n_packets, const hisparse::dev::CsrView* csr,
                      uint32_t num_rows, uint32_t num_cols, uint32_t num_row_partitions, uint32_t num_col_partitions) {
-    int rc = load_matrix_once(ctx, channel, n_packets, csr, num_rows, num_cols, num_row_partitions, num_col_partitions);
     const char* tune = ctx_option(ctx, "HISPARSE_AUTOTUNE");
-    if (rc != HS_OK || !(tune && std::atoi(tune) != 0) || ctx_option(ctx, "HISPARSE_STREAM_FORMAT")) return rc;      // (a forced format is the caller's decision)
+    const bool tuning = tune && std::atoi(tune) != 0 && !ctx_option(ctx, "HISPARSE_STREAM_FORMAT");      // (a forced format is the caller's decision)
+    // (the value map, when asked for, is built by the load that is kept: the candidate loads of autotune go without)
+    int rc = load_matrix_once(ctx, channel, n_packets, csr, num_rows, num_cols, num_row_partitions, num_col_partitions, !tuning);
+    if (rc != HS_OK || !tuning) return rc;
     const bool debug = ctx_option(ctx, "HISPARSE_PLAN_DEBUG") != nullptr;
     const char* const names[] = {"pairs", "delta", "bitmap", "owner", "pairs24", "owner24", "sweep"};      // StreamFormat order (stream_tiles.h)
     const std::string own = ctx->light ? "light" : names[ctx->format < 7 ? ctx->format : 0];
     const uint64_t nnz = ctx->stats.nnz;
     const int runs = int(std::max<uint64_t>(5, std::min<uint64_t>(50, (uint64_t(40) << 20) / std::max<uint64_t>(1, nnz))));      // ~ 1-3 ms of SpMVs per candidate
     double best_us = time_loaded_plan(ctx, runs);
-    if (best_us <= 0.0) return HS_OK;                       // could not time: the planner's plan stands
+    if (best_us <= 0.0)                                     // could not time: the planner's plan stands
+        return value_map_asked(ctx) ? load_matrix_once(ctx, channel, n_packets, csr, num_rows, num_cols, num_row_partitions, num_col_partitions, true) : HS_OK;
     std::string best = own;
     if (debug) std::fprintf(stderr, "autotune: planner's plan %s x%u: %.2f us\n", own.c_str(), ctx->col_slices, best_us);
     const double own_us = best_us;
@@ -700,7 +754,7 @@ int load_matrix_impl(hs_context* ctx, const void* const* channel, const uint64_t
         if (own == fmt) continue;
         ctx->options["HISPARSE_STREAM_FORMAT"] = fmt;
         ctx->options["HISPARSE_LIGHT"] = "0";
-        const int rc2 = load_matrix_once(ctx, channel, n_packets, csr, num_rows, num_cols, num_row_partitions, num_col_partitions);
+        const int rc2 = load_matrix_once(ctx, channel, n_packets, csr, num_rows, num_cols, num_row_partitions, num_col_partitions, false);
         double us = -1.0;
         if (rc2 == HS_OK && std::string(names[ctx->format < 7 ? ctx->format : 0]) == fmt) us = time_loaded_plan(ctx, runs);
         if (debug) std::fprintf(stderr, "autotune: %s x%u: %s\n", fmt, rc2 == HS_OK ? ctx->col_slices : 0u, us > 0.0 ? (std::to_string(us) + " us").c_str() : "not available");
@@ -711,7 +765,7 @@ int load_matrix_impl(hs_context* ctx, const void* const* channel, const uint64_t
         ctx->options["HISPARSE_STREAM_FORMAT"] = best;
         ctx->options["HISPARSE_LIGHT"] = "0";
     }
-    rc = load_matrix_once(ctx, channel, n_packets, csr, num_rows, num_cols, num_row_partitions, num_col_partitions);      // the winner (or the planner's own plan again)
+    rc = load_matrix_once(ctx, channel, n_packets, csr, num_rows, num_cols, num_row_partitions, num_col_partitions, true);      // the winner (or the planner's own plan again)
     restore();
     if (debug) std::fprintf(stderr, "autotune: kept %s (%.2f us against the planner's %.2f)\n", best.c_str(), best_us, own_us);
     return rc;
@@ -747,6 +801,39 @@ int hs_load_matrix_csr(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, co
     }
     return rc;
 }
+
+// EXTENSION: new values for the loaded CSR matrix, in place (hisparse_hip.h).  A carried combine pass is settled first (HS_FLUSH), as at
+// every other entry point: it reads only the partial vectors, never the image, so leaving it owed would be correct too, but settling keeps
+// the rule "every entry point but hs_run settles" without an exception to reason about, for one combine launch of a few microseconds.
+namespace {
+int update_values(hs_context* ctx, const float* values, uint64_t nnz, bool from_host) {
+    if (!ctx) return HS_ERR_BAD_ARG;
+    if (!ctx->matrix_loaded) return fail(ctx, HS_ERR_NOT_LOADED, "hs_load_matrix has not been called");
+    if (!values) return fail(ctx, HS_ERR_BAD_ARG, "null argument");
+    if (!ctx->d_value_map) return fail(ctx, HS_ERR_UNSUPPORTED, "no value map: " + ctx->value_map_why);
+    if (nnz != ctx->value_map_nnz)
+        return fail(ctx, HS_ERR_BAD_ARG, "nnz must equal the loaded CSR's indptr[num_rows] (" + std::to_string(ctx->value_map_nnz) + ")");
+    if (!from_host && reinterpret_cast<uintptr_t>(values) % 4 != 0) return fail(ctx, HS_ERR_BAD_ARG, "values_dev must be 4-byte aligned");
+    HS_HIP(ctx, hipSetDevice(ctx->device));
+    HS_FLUSH(ctx);
+    if (nnz == 0) return HS_OK;
+    const float* src = values;
+    if (from_host) {
+        if (!ctx->d_value_stage) HS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_value_stage), size_t(nnz) * 4));
+        // (stream order: the previous update's kernel has read the staging buffer before this copy writes it)
+        HS_HIP(ctx, hipMemcpyAsync(ctx->d_value_stage, values, size_t(nnz) * 4, hipMemcpyHostToDevice, ctx->stream));
+        src = ctx->d_value_stage;
+    }
+    HS_HIP(ctx, hisparse::dev::launch_value_update(ctx->impl == HS_IMPL_FIXED, src, nnz, ctx->d_value_map, reinterpret_cast<uint32_t*>(ctx->d_image),
+                                                   ctx->stats.stream_bytes / 4, ctx->d_value_map2, ctx->d_mfma, ctx->d_value_map2 ? ctx->mfma_bytes / 4 : 0,
+                                                   uint32_t(ctx->compute_units), ctx->stream));
+    if (from_host) HS_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the caller may reuse `values` immediately (as after hs_load_vector)
+    return HS_OK;
+}
+}  // namespace
+
+int hs_update_values(hs_context* ctx, const float* values, uint64_t nnz) { return update_values(ctx, values, nnz, true); }
+int hs_update_values_device(hs_context* ctx, const float* values_dev, uint64_t nnz) { return update_values(ctx, values_dev, nnz, false); }
 
 int hs_debug_read_tiles(hs_context* ctx, void* image, uint64_t image_capacity, void* blocks, void* units) {
     if (!ctx) return HS_ERR_BAD_ARG;

@@ -145,6 +145,11 @@ hipError_t launch_push_result(const uint32_t* y, void* const* dst, uint32_t n_ds
 // Iterative callers: x[i] = scale (*) y[i] (+) shift, i < n, in Q8.24 (AP_RND, AP_SAT) or fp32 arithmetic.
 hipError_t launch_feedback(bool is_float, const uint32_t* y, uint32_t* x, uint32_t n, uint32_t scale, uint32_t shift, hipStream_t stream);
 
+// hs_update_values (value_update.hip): image[map[e]] = value_word(values[e]) for e < n, and image2[map2[e]] likewise when map2 is not null;
+// map entries at or past image_words / image2_words are skipped.  One grid-stride launch sized by the CU count.
+hipError_t launch_value_update(bool fixed, const float* values, uint64_t n, const uint32_t* map, uint32_t* image, uint64_t image_words, const uint32_t* map2,
+                               uint32_t* image2, uint64_t image2_words, uint32_t compute_units, hipStream_t stream);
+
 }  // namespace dev
 }  // namespace hisparse
 

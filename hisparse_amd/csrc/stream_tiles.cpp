@@ -964,6 +964,7 @@ bool build_stream_tiles_once(const void* const channel[NUM_HBM_CHANNELS], const 
     if (gpu) {
         if (!gpu->emit(out.format, image_bytes, image_slack, plans, block_of_unit, out.blocks, is_float)) { error = gpu->error(); return false; }
         out.d_image = gpu->release_image();
+        out.d_value_map = gpu->release_value_map();
         out.image_bytes = image_bytes;
         finish_blocks();
         timer.lap("gpu: emit");

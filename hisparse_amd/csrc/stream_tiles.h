@@ -308,6 +308,8 @@ struct StreamTiles {
     MfmaImage mfma;                      // float BITMAP images only (bitmap_tiles.cpp)
     uint32_t bitmap_x_groups = 0;        // BITMAP: groups of x a block reads (its column slice), when the kernel is to keep that stretch in LDS; else 0
     uint8_t* d_image = nullptr;          // GPU builder: the image, already in device memory (image_bytes + slack); the caller owns it
+    uint32_t* d_value_map = nullptr;     // GPU builder, CsrView::value_map: per CSR non-zero the u32 word index of its value in d_image; the caller owns it
+    uint32_t* d_value_map2 = nullptr;    // ... and in mfma.d_words (float BITMAP matrices with the matrix-engine image)
     uint64_t image_bytes = 0;
     std::vector<Block> blocks;
     std::vector<Unit> units;
@@ -335,6 +337,7 @@ struct CsrView {
     const uint32_t* indptr = nullptr;        // num_rows + 1
     const uint32_t* indices = nullptr;
     const float* values = nullptr;
+    bool value_map = false;                  // option value_map: the device builder also records every non-zero's value word index (gpu_tiles.h)
 };
 
 // Decode + validate + re-tile.  `max_workgroups` = workgroups the device keeps resident (one per CU).

@@ -309,6 +309,7 @@ bool build_sweep_tiles(const Layout& L, const void* const channel[NUM_HBM_CHANNE
         }
         if (!gpu->sweep_emit(layout, out.image_bytes, image_slack)) { error = gpu->error(); return false; }
         out.d_image = gpu->release_image();
+        out.d_value_map = gpu->release_value_map();
         timer.lap("sweep: gpu emit");
     } else {
     resize_zeroed(out.image, out.image_bytes);

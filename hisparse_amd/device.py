@@ -18,7 +18,7 @@ _lib = None
 EXPORTS = [
     "hs_strerror", "hs_last_error", "hs_create", "hs_destroy", "hs_load_matrix", "hs_load_vector", "hs_run",
     "hs_load_matrix_csr", "hs_run_batch", "hs_run_partition", "hs_sync", "hs_read_result", "hs_set_stream", "hs_get_stream", "hs_device_vector", "hs_device_result",
-    "hs_bind_device_vector", "hs_bind_device_result", "hs_push_result", "hs_set_option", "hs_feedback", "hs_iterate", "hs_load_matrix_csc", "hs_spmspv", "hs_spmspv_device", "hs_read_spmspv_result", "hs_spmspv_status", "hs_spmm", "hs_spmm_device", "hs_get_stats", "hs_time_runs", "hs_time_kernel", "hs_debug_read_tiles", "hs_debug_read_mfma_image", "hs_tiles_build", "hs_tiles_info",
+    "hs_bind_device_vector", "hs_bind_device_result", "hs_push_result", "hs_set_option", "hs_feedback", "hs_iterate", "hs_load_matrix_csc", "hs_spmspv", "hs_spmspv_device", "hs_read_spmspv_result", "hs_spmspv_status", "hs_spmm", "hs_spmm_device", "hs_get_stats", "hs_time_runs", "hs_time_kernel", "hs_debug_read_tiles", "hs_debug_read_mfma_image", "hs_update_values", "hs_update_values_device", "hs_tiles_build", "hs_tiles_info",
     "hs_tiles_copy", "hs_tiles_free", "hs_tiles_last_error",
 ]
 
@@ -93,6 +93,8 @@ def lib():
         l.hs_load_matrix_csr.argtypes = [vp, u32, u32, vp, vp, vp, C.POINTER(u32), C.POINTER(u32)]
         l.hs_spmm.argtypes = [vp, vp, u32, u32, vp, u32]
         l.hs_spmm_device.argtypes = [vp, vp, u64, vp, u64, u32]
+        l.hs_update_values.argtypes = [vp, vp, u64]
+        l.hs_update_values_device.argtypes = [vp, vp, u64]
         # (HISPARSE_HIP_LIB may name libhisparse_cpu.so, the separate host-thread build of the same boundary for machines without a
         # GPU: it has no re-tiling to introspect.  The default library must export everything: tests/test_capi.py.)
         if hasattr(l, "hs_tiles_build") or os.path.basename(_LIB_PATH) == "libhisparse_hip.so":
@@ -135,6 +137,7 @@ class SpmvEngine:
         self.ob_bank, self.vb_bank = ob_bank or default_ob, vb_bank or default_vb
         self.num_rows = self.num_cols = 0
         self.row_parts = self.col_parts = 0
+        self.csr_nnz = None          # non-zeros of the last load_matrix_csr (what update_values takes)
 
     def _check(self, rc):
         if rc != 0:
@@ -167,6 +170,7 @@ class SpmvEngine:
         ptrs, counts, keep = _channel_arrays(packets)
         self._check(lib().hs_load_matrix(self._h, ptrs, counts, num_rows, num_cols, num_row_partitions, num_col_partitions))
         del keep
+        self.csr_nnz = None
         self.num_rows, self.num_cols = num_rows, num_cols
         self.row_parts, self.col_parts = num_row_partitions, num_col_partitions
 
@@ -185,6 +189,29 @@ class SpmvEngine:
                                              data.ctypes.data if data.size else None, C.byref(pr), C.byref(pc)))
         self.num_rows, self.num_cols = pr.value, pc.value
         self.row_parts, self.col_parts = -(-pr.value // (128 * self.ob_bank)), -(-pc.value // (8 * self.vb_bank))
+        self.csr_nnz = int(indptr[rows]) if indptr.size > rows else 0
+
+    def update_values(self, values):
+        """hs_update_values: new values for the matrix of the last load_matrix_csr, in its non-zero order (float32, host memory; needs
+        set_option("value_map", 1) before that load).  Returns once `values` may be reused."""
+        values = np.ascontiguousarray(values, dtype=np.float32).ravel()
+        if self.csr_nnz is not None and values.size != self.csr_nnz:      # (the library checks the count too; this keeps a short array from being over-read)
+            raise DeviceError(-1, f"update_values: {values.size} values for a matrix of {self.csr_nnz} non-zeros")
+        self._check(lib().hs_update_values(self._h, values.ctypes.data if values.size else None, values.size))
+
+    def update_values_device(self, ptr, nnz=None):
+        """hs_update_values_device: the values already in device memory -- a pointer (int) and their count, or a float32 torch tensor on the
+        context's device (count taken from it).  Asynchronous on the context's stream: the memory must stay unchanged until the stream reaches
+        the update."""
+        if hasattr(ptr, "data_ptr"):
+            import torch
+            if ptr.dtype != torch.float32 or not ptr.is_cuda or not ptr.is_contiguous():
+                raise DeviceError(-1, "update_values_device: a contiguous float32 tensor on the GPU")
+            nnz = ptr.numel() if nnz is None else nnz
+            ptr = ptr.data_ptr()
+        if nnz is None:
+            raise DeviceError(-1, "update_values_device: the count of values is needed with a raw pointer")
+        self._check(lib().hs_update_values_device(self._h, C.c_void_p(ptr or None), int(nnz)))
 
     def load_vector(self, x_words):
         x_words = np.ascontiguousarray(x_words, dtype=np.uint32)

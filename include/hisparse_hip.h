@@ -157,7 +157,7 @@ int hs_push_result(hs_context* ctx, void* const* dst, uint32_t n_dst, uint32_t n
  * (pairs|delta|owner|owner24|sweep|bitmap), col_slices, max_rows, cross_partitions (0: row blocks end at the reference's row-partition borders), spmm_vectors (4: plan the image for the four-column SpMM kernel, see hs_spmm), row_runs, delta_deal (wave: the dealing of DELTA runs of rounds 1-4), pow2_slices (1: column-slice counts 1, 2, 4, 8 only for matrices of more than sixteen sub-tiles, the rule of rounds 1-4), aux_bits, xcd_affinity, retile (host), bitmap_skew, bitmap_x_lds,
  * bitmap_build, walk_lanes, no_mfma_image, mfma_chunk, light (0|1: the small-matrix kernel), sweep (0|1: the
  * column-ordered format of very sparse matrices), plan_debug; call-time keys: spmm_fused, spmm_mfma,
- * spmspv (sparse|auto|dense), spmspv_crossover, iterate_graph, batch_graph (hs_run_batch); carry_combine (0|1, plan-time: see hs_run), stream_resident (0|1, plan-time: SWEEP and PAIRS / DELTA images streamed without the non-temporal hint; default: SWEEP images up to 256 MiB, the Infinity Cache; PAIRS / DELTA images up to 256 MiB whose blocks walk several units, or up to 32 MiB: hs_stats.stream_resident says what the plan took).  autotune (0|1, plan-time, round 6: the load builds the planner's own image AND every other element format the matrix can take, times a few SpMVs of each on a zero vector and keeps the fastest -- a handful of extra loads of tens of milliseconds each, for callers that run one matrix thousands of times; a forced stream_format switches it off; hs_get_stats says what was kept), plan_census (0: plan from the rows' non-zero counts alone, as rounds 1-5 did).  value NULL or "" clears the option.  An unknown key is HS_ERR_BAD_ARG.
+ * spmspv (sparse|auto|dense), spmspv_crossover, iterate_graph, batch_graph (hs_run_batch); carry_combine (0|1, plan-time: see hs_run), stream_resident (0|1, plan-time: SWEEP and PAIRS / DELTA images streamed without the non-temporal hint; default: SWEEP images up to 256 MiB, the Infinity Cache; PAIRS / DELTA images up to 256 MiB whose blocks walk several units, or up to 32 MiB: hs_stats.stream_resident says what the plan took).  autotune (0|1, plan-time, round 6: the load builds the planner's own image AND every other element format the matrix can take, times a few SpMVs of each on a zero vector and keeps the fastest -- a handful of extra loads of tens of milliseconds each, for callers that run one matrix thousands of times; a forced stream_format switches it off; hs_get_stats says what was kept), plan_census (0: plan from the rows' non-zero counts alone, as rounds 1-5 did), value_map (0|1, plan-time: hs_load_matrix_csr keeps the value map of hs_update_values).  value NULL or "" clears the option.  An unknown key is HS_ERR_BAD_ARG.
  * Options set here win over the environment variable of the same name, which stays as the fallback for tools and tests.  None of them
  * changes WHAT is computed.  The switches that do (HISPARSE_ABLATE, HISPARSE_DEPTH: profiling builds with parts of the work removed) are
  * not options: they exist only in libhisparse_hip_prof.so, and this library refuses to run (HS_ERR_BAD_ARG from hs_run, hs_run_partition,
@@ -230,6 +230,33 @@ int hs_spmspv_status(hs_context* ctx, uint32_t* overflowed, void** overflow_word
  * NULL) receive the dimensions hs_load_vector / hs_read_result then expect. */
 int hs_load_matrix_csr(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, const float* values,
                        uint32_t* padded_rows, uint32_t* padded_cols);
+
+/* ---- value update (EXTENSION: same sparsity pattern, new numbers; no reference counterpart) ----------------------------------------
+ * A load plans the tiles, sorts every non-zero and emits the image -- tens of milliseconds on the large matrices, hundreds of SpMVs.  A
+ * caller that keeps the pattern and changes only the values (pruned layers during fine-tuning, re-weighted graphs, solvers whose
+ * coefficients change) refreshes the values in place instead:
+ *   hs_set_option "value_map" = 1 (plan-time; environment HISPARSE_VALUE_MAP) before hs_load_matrix_csr: the load keeps a VALUE MAP on the
+ *     device -- per non-zero, in the order of the CSR arrays, the 32-bit word index of its value in the image (4 bytes per non-zero; a float
+ *     BITMAP matrix with the matrix-engine image of hs_spmm keeps a second one, 8 bytes per non-zero in all).  The load itself costs 4 bytes
+ *     per non-zero more while it sorts.  Option 0 (the default): the load is what it always was.  Under autotune only the kept image gets a map.
+ *   hs_update_values: `values` in HOST memory, nnz floats in the non-zero order of the CSR arrays of the last hs_load_matrix_csr (nnz =
+ *     its indptr[num_rows], before padding), converted like csr_matrix_convert_from_float as the load converts them.  Copied into a device
+ *     staging buffer of the context (allocated on first use, freed with the matrix), then one kernel scatters the value words into the
+ *     image; returns once `values` may be reused (as hs_load_vector).
+ *   hs_update_values_device: the same with `values_dev` in DEVICE memory (4-byte aligned; 16-byte aligned streams it four at a time):
+ *     asynchronous, no copy -- values_dev must stay unchanged until the stream has reached the kernel.
+ * STREAM ORDER: every hs_run*, hs_iterate, hs_spmm* and hs_feedback enqueued after the call on the context's stream computes with the new
+ * values -- exactly what a load of the same indptr / indices and the new values computes: the image (hs_debug_read_tiles) and the
+ * matrix-engine image (hs_debug_read_mfma_image) hold the same bytes, Block[] and Unit[] are untouched, the plan is not redone (an image
+ * autotune kept stays).  Work enqueued before the call uses the old values.
+ * Returns HS_ERR_NOT_LOADED (no matrix), HS_ERR_BAD_ARG (null pointer, nnz not the loaded count, misaligned values_dev) or HS_ERR_UNSUPPORTED
+ * when the context holds no value map -- hs_last_error says why: the option was off at the load; the matrix came from hs_load_matrix
+ * (CPSR); the image was built by the host builder (duplicate (row, column) entries, bitmap_build=host, SWEEP chunks spanning more than
+ * 65535 columns); or it is 16 GiB or larger.
+ * The CSC matrix of hs_spmspv is NOT updated: under spmspv = auto, "the same matrix both ways" stays the caller's contract -- load the CSC
+ * matrix again with the new values, or leave the dense dispatch off. */
+int hs_update_values(hs_context* ctx, const float* values, uint64_t nnz);
+int hs_update_values_device(hs_context* ctx, const float* values_dev, uint64_t nnz);
 
 /* ---- SpMM (EXTENSION; the reference has no SpMM) ----------------------------------------------------------
  * Y = A X for k dense vectors, column j of X / Y being a packed vector of num_cols / num_rows words (the layouts of hs_load_vector
