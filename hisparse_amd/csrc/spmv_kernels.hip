@@ -259,7 +259,7 @@ struct Consumer {
     uint32_t pos = 0;          // DELTA: this lane's position in the current sub-tile
     bool head = true;          // DELTA: the next record of this wavefront is a head record
     uint32_t run_row = kNoRow; // PAIRS dense rows: row whose products are being summed in registers ...
-    prod_t run_sum = 0;        // ... and this lane's share of that sum
+    typename Rows<kFloat>::sum_t run_sum = 0;   // ... and this lane's share of that sum (float: in double, like every sum of products here)
     uint32_t lane_row = 0;     // DELTA dense rows: the row this LANE is on (its run of consecutive elements rarely leaves it) ...
     typename Rows<kFloat>::lane_t lane_sum = 0;  // ... and the lane's private sum on it, flushed to LDS when the row or the unit changes
     typename OwnerSum<kFloat>::type own_sum = 0;   // OWNER: the lane's sum on lane_row (4-byte accumulators touched by this wavefront only: fp32, or saturating Q8.24)
@@ -297,8 +297,8 @@ __device__ __forceinline__ bool consume_step(Consumer<kFloat>& c) {
     const uint32_t s = c.base + K;
     while (s == c.end) {               // this wavefront finished sub-tile u (possibly with no work in it)
         if (!kDelta && kDense && c.u + 1 == c.U && c.run_row != Consumer<kFloat>::kNoRow) {   // last sub-tile: hand the register sum over
-            const typename R::prod_t sum = wave_sum(c.run_sum);
-            if (c.lane == 0) R::add(c.ys, c.run_row, sum);
+            const typename R::sum_t sum = wave_sum(c.run_sum);
+            if (c.lane == 0) R::add_sum(c.ys, c.run_row, sum);
             c.run_row = Consumer<kFloat>::kNoRow;
         }
         if (kDelta && kDense) {        // every lane hands its private row sum over before the sub-tile changes
@@ -373,13 +373,13 @@ __device__ __forceinline__ bool consume_step(Consumer<kFloat>& c) {
                 const uint32_t row0 = __builtin_amdgcn_readfirstlane(row);
                 const bool uniform = __ballot(row == row0) == ~0ull;
                 if (uniform && row0 == c.run_row) {
-                    c.run_sum += prod;
+                    c.run_sum += R::widen(prod);
                 } else {
                     if (c.run_row != Consumer<kFloat>::kNoRow) {
-                        const typename R::prod_t sum = wave_sum(c.run_sum);
-                        if (c.lane == 0) R::add(c.ys, c.run_row, sum);
+                        const typename R::sum_t sum = wave_sum(c.run_sum);
+                        if (c.lane == 0) R::add_sum(c.ys, c.run_row, sum);
                     }
-                    if (uniform) { c.run_row = row0; c.run_sum = prod; }
+                    if (uniform) { c.run_row = row0; c.run_sum = R::widen(prod); }
                     else { c.run_row = Consumer<kFloat>::kNoRow; c.run_sum = 0; R::add(c.ys, row, prod); }   // chunk straddles rows
                 }
             } else {

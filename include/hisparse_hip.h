@@ -103,6 +103,26 @@ int hs_load_matrix(hs_context* ctx, const void* const channel[HS_NUM_CHANNELS], 
 /* packed_x: num_cols value words (PACKED_VAL_T[num_cols/8]) in natural order. */
 int hs_load_vector(hs_context* ctx, const void* packed_x, uint32_t num_cols);
 
+/* ARITHMETIC.  Fixed point (HS_IMPL_FIXED): every product rounded and saturated to Q8.24 (pe.h), a row's sum saturated once at 2^32 - 1 --
+ * bit for bit the oracle's answer, in any order, across column slices (saturating combine) and hs_spmspv passes alike.
+ * Float (HS_IMPL_FLOAT_POB / _STALL): one fp32 multiply per stored element (no FMA contraction; the vector-ALU paths keep denormal
+ * products and sums: the build sets no flush flag -- what the matrix engine's FMAs do with subnormal products is not promised), a zero
+ * element included (0 x inf = NaN reaches its row; padding slots never touch a real row).  Let p = the fp32 products of a
+ * row, E = their exact sum, A = sum |p|, n = their count, u = 2^-24 and gamma(k) = k u / (1 - k u).  How far y may lie from E depends
+ * on L, the longest chain of fp32 additions a product passes through before it joins a double sum:
+ *   L = 1   PAIRS, PAIRS24, LIGHT, SWEEP, DELTA without per-lane sums, hs_spmspv, hs_spmm with spmm_vectors = 4 (double sums only);
+ *   L = a lane's run of slots in one unit (at most the row's elements within 8192 columns)   DELTA with per-lane register sums;
+ *   L = 8   BITMAP SpMV and the fused BITMAP hs_spmm (8 products of a batch added in fp32);
+ *   L = n   OWNER / OWNER24 (fp32 accumulators);
+ *   L = n + 1   hs_spmm on the matrix engine (n fp32 FMAs from a zero accumulator, with the unrounded products a x in place of p);
+ *   one column slice:    |y - E| <= u |E| + (1 + u) gamma(L - 1) A + n 2^-52 A + L 2^-149
+ *   S slices / passes:   |y - E| <= gamma(L - 1 + S) A + n 2^-52 A + (L + S) 2^-149      (partials rounded once, added in fp32)
+ * So with L = 1 and one slice a finite E is rounded once: y = fl32(E) up to the double sum (in particular finite where an fp32 running
+ * sum would overflow).  Non-finite results follow IEEE double summation of p: NaN when a product is NaN or +inf and -inf meet, else
+ * the infinity that occurs.  An empty row is +0.0.  Every entry point of a matrix keeps its class: hs_run (repeated, in bursts whose
+ * combine is carried), hs_run_partition, hs_run_batch (graph or not); hs_spmm column by column; hs_spmspv.  tests/float_contract.py
+ * states the same and the GPU suite asserts it for these entry points. */
+
 /* One full SpMV (every row partition) in one launch sequence; asynchronous.
  * Column-sliced plans (hs_stats.col_slices > 1: the SpMV kernel leaves per-slice partial rows, a small combine pass adds them up):
  * when hs_run follows hs_run on the library's own stream, the combine pass of the earlier
@@ -203,8 +223,8 @@ int hs_iterate(hs_context* ctx, uint32_t iterations, uint32_t scale_word, uint32
  *   hs_spmspv_device: the same with the pairs already in DEVICE memory (8-byte aligned): nothing but the two launches (3-4 us less).  No
  *     index check (out-of-range columns are ignored), no dense dispatch, and no column may be named twice (a bin that overflows contributes
  *     nothing -- its rows come out zero -- and hs_read_spmspv_result reports HS_ERR_BAD_ARG; hs_spmspv_status tells without a read-back).
- * Arithmetic as in hs_run: fixed = saturating sum of individually rounded / saturated products (bit-exact, order free);
- * float = fp32 products summed in double per row block, rounded once (tolerance). */
+ * Arithmetic as in hs_run (ARITHMETIC above): fixed = saturating sum of individually rounded / saturated products (bit-exact, order free);
+ * float = fp32 products summed in double per row block, rounded once (L = 1); a call cut into P passes adds them in fp32 (S = P). */
 typedef struct { uint32_t index; uint32_t val; } hs_idx_val;    /* IDX_VAL_T, spmv/libfpga/common.h:54 */
 int hs_load_matrix_csc(hs_context* ctx, const uint32_t* indptr, const uint32_t* row_indices, const uint32_t* value_words, uint32_t num_rows,
                        uint32_t num_cols);
@@ -261,7 +281,8 @@ int hs_update_values_device(hs_context* ctx, const float* values_dev, uint64_t n
 /* ---- SpMM (EXTENSION; the reference has no SpMM) ----------------------------------------------------------
  * Y = A X for k dense vectors, column j of X / Y being a packed vector of num_cols / num_rows words (the layouts of hs_load_vector
  * and hs_read_result).  Column j of Y is what hs_run gives for column j of X: bit for bit in fixed point; in the float modes within the
- * float tolerance of the parity contract (the fused kernels add a row's partial sums in another order than the SpMV kernel).
+ * bound of its route (ARITHMETIC above: fused BITMAP L = 8, matrix engine L = n, spmm_vectors = 4 L = 1; the fused kernels add a row's
+ * partial sums in another order than the SpMV kernel).
  *   BITMAP images (dense rows -- the pruned-NN layers, which meet batches of activations in practice), one column slice: FUSED, 4
  *     then 2 columns at a time (spmm_bitmap.hip): masks and values are streamed once per group, x interleaved [column][vector];
  *     transformer-50: 6.3 us per column against 13.5 us for an SpMV (profiles/r02_spmm_bitmap.txt).  HISPARSE_SPMM_FUSED=0 turns it off.
