@@ -852,6 +852,8 @@ bool GpuTiler::count_tiles(const std::vector<uint32_t>& block_of_row, uint32_t n
     const uint32_t S = L_.subs_per_cp, tiles = L_.col_parts * S;
     cnt.assign(size_t(num_ranges) * tiles, 0);
     uint32_t* d_cnt = nullptr;
+    if (d_block_of_row_) (void)hipFree(d_block_of_row_);      // (a load calls this twice: the census's row map, then the plan's)
+    d_block_of_row_ = nullptr;
     if (!check(upload(&d_block_of_row_, block_of_row, stream_), "upload block_of_row")) return false;
     if (!check(hipMalloc(reinterpret_cast<void**>(&d_cnt), std::max<size_t>(cnt.size() * 4, 16)), "hipMalloc")) return false;
     bool ok = check(hipMemsetAsync(d_cnt, 0, cnt.size() * 4, stream_), "hipMemset");

@@ -21,7 +21,7 @@
 // product (they run at ~24 G/s on this chip): one per (workgroup of 64 columns, row block touched).
 // Cost: ~12-18 us (two launches and two dependent chains: entry -> column pointer -> elements; cursor -> bin) + products / ~40 G/s (a column
 // entry is read, its product written and read again: 24 bytes per product at ~1 TB/s, mostly L2); above the crossover with the caller's
-// dense SpMV hs_spmspv dispatches to that when it can (hs_api.cpp; hisparse_hip.h says so).
+// dense SpMV hs_spmspv dispatches to that when it can (hs_spmspv.cpp; hisparse_hip.h says so).
 //   fixed: products rounded / saturated one by one (q8_24_mul), summed exactly in 64 bits, clamped once -- bit-identical to the
 //          saturating PE sum, in any order;
 //   float: one fp32 multiply per product, double sums per row block, rounded once: tolerance parity like every float path.

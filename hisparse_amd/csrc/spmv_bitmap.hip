@@ -351,7 +351,7 @@ hipError_t launch_spmv_bitmap(bool is_float, const SpmvLaunch& a, hipStream_t st
         timeline = timelines[dev];
     }
     bool launched = false;
-    // a.bitmap_x_groups != 0: the launch's LDS has room for that many groups of x behind the accumulators (hs_api.cpp sizes it)
+    // a.bitmap_x_groups != 0: the launch's LDS has room for that many groups of x behind the accumulators (hs_load.cpp sizes it)
     const uint32_t x_lds_offset = a.bitmap_x_groups ? a.lds_bytes - a.bitmap_x_groups * kBitmapGroupCols * 4u : 0u;
 #define X(F, A)                                                                                                                                  \
     if (!launched && a.bitmap_x_groups && is_float == F && ablate == A) {                                                                        \

@@ -137,7 +137,7 @@ __device__ __forceinline__ T segmented_run_sums(T v, uint32_t row, bool& is_last
 // (DESIGN.md).  This one needs none: when hs_run follows hs_run, the partial rows of step k are complete and visible when the kernel of
 // step k + 1 STARTS (a kernel boundary lies between them), so that kernel's workgroups -- each a stripe of the rows, by workgroup index --
 // add them up and write y(k) first, while their own descriptor and first stream loads travel; step k + 1 writes the OTHER set of partial
-// vectors.  The host launches the stand-alone combine only for the LAST step of such a run (hs_api.cpp: flush_combine).  Sums in slice
+// vectors.  The host launches the stand-alone combine only for the LAST step of such a run (hs_context.h: CarriedCombine::settle).  Sums in slice
 // order from 0.0f / saturating adds, exactly as combine_slices_kernel: the same words.
 struct CarriedCombine {
     const uint32_t* partial = nullptr;      // the previous step's partial vectors (nullptr: nothing to carry)

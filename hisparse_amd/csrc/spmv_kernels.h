@@ -119,7 +119,7 @@ hipError_t launch_combine_slices(bool is_float, const uint32_t* partial, uint32_
 // SpMSpV extension (spmspv.hip): y = A x for x given as x_count IDX_VAL_T pairs ON THE DEVICE over a CSC matrix.  Two launches: EXPAND writes
 // the selected columns' products straight into per-row-block BINS (an LDS histogram per workgroup of 64 entries, one global atomic per workgroup
 // and non-empty bin claims the room), ACCUMULATE has one workgroup per row block add ITS bin in LDS and write its rows of y.  No scan, no sort,
-// no host synchronisation.  Scratch, owned by the caller (hs_api.cpp):
+// no host synchronisation.  Scratch, owned by the caller (hs_context.h: CscData):
 struct hs_idx_val_dev { uint32_t index, val; };      // == hs_idx_val (hisparse_hip.h), IDX_VAL_T of spmv/libfpga/common.h:54
 struct SpmspvScratch {
     uint32_t* keys = nullptr;                   // [nnz] rows of the products, bin by bin

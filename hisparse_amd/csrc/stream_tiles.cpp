@@ -251,7 +251,7 @@ bool build_stream_tiles_once(const void* const channel[NUM_HBM_CHANNELS], const 
         const double mask_bytes = double(num_rows) * double((num_cols + kBitmapGroupCols - 1) / kBitmapGroupCols) * 8.0;
         bool bitmap = density >= kBitmapMinDensity && num_cols >= kBitmapMinCols && mask_bytes <= 2.0 * double(out.nnz);
         // Round 5: SMALL dense-row layers in FIXED point as a sliced DELTA plan.  With the combine pass carried into the next step's kernel
-        // (hs_api.cpp) a plan of one column slice per x sub-tile is ONE launch without x refills and unit barriers, and its lanes sum their
+        // (hs_context.h: CarriedCombine) a plan of one column slice per x sub-tile is ONE launch without x refills and unit barriers, and its lanes sum their
         // rows in registers (kBlockDenseRows): measured on the 512 x 33 288 pruned-NN layers (profiles/r05_sliced_delta_vs_bitmap.txt, fixed
         // point, whole step; with the lane-major dealing of the runs, "after the dealing" there): 10 % dense 7.5 us against 8.6 (LIGHT), 20 % 9.0
         // against 11.9 (BITMAP), 30 % 11.0 against 12.0, 40 % 12.5 against 12.4, 5 % 6.9 against 5.9 (LIGHT) -- ~5.8 us + 1.0 us per million
@@ -503,7 +503,7 @@ bool build_stream_tiles_once(const void* const channel[NUM_HBM_CHANNELS], const 
                     const double conflict_us = (!owner && pairs_likely && lanes_per_row > 1.0 && per_row_and_tile >= 16.0)
                                                    ? double(out.nnz) / G / kWaveLanes * (lanes_per_row - 1.0) * 2.0 / 2400.0 : 0.0;
                     // the combine pass: a launch of its own (3.5 us) + its traffic -- or ~1 us of the NEXT step's kernel where the image is small
-                    // enough for the carried combine (hs_api.cpp; stream_tiles.h: kCarryMaxImageBytes)
+                    // enough for the carried combine (hs_context.h: CarriedCombine; stream_tiles.h: plan_carries)
                     const bool carried = double(out.nnz) * 8.1 < double(kCarryMaxImageBytes);
                     const double combine_us = cs > 1 ? (carried ? 1.0 : 3.5) + double(num_rows) * 4.0 * (cs + 1) / 4e6 : 0.0;
                     // workgroup slots that get no block (7 slices x 36 row ranges = 252 blocks on 256 workgroups): the stream they would have taken

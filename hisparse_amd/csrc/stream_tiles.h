@@ -85,14 +85,14 @@ constexpr uint32_t max_block_rows(bool sliced) { return (sliced ? 96u : 32u) * 1
 constexpr uint32_t kMaxColSlices = 8;
 constexpr uint32_t kMaxForcedColSlices = 16;   // HISPARSE_COL_SLICES / col_slices may ask the row-block planner for up to this many (the combine pass is instantiated for 2 .. 16)
 constexpr uint32_t kMaxSweepSlices = 16;      // SWEEP images (round 5): a short, wide matrix -- one rank's slab -- wants few row ranges (every range sweeps all of x) and many slices
-// Column-sliced plans whose image stays below this carry the combine pass of a step into the next step's kernel (hs_api.cpp: one launch per
+// Column-sliced plans whose image stays below this carry the combine pass of a step into the next step's kernel (hs_context.h: CarriedCombine: one launch per
 // step in a run of hs_run calls); the planner prices the combine pass of such a plan at ~1 us instead of a launch of its own (3.5 us).
 // Round 5 set 48 MiB from two points (a 29 MB slab: 10.1 -> 8.6 us; ogbl-ppa, 280 MB: a wash; pokec's SWEEP image, 247 MB: 73.5 -> 76.0).  Round 6 measured the
 // middle (profiles/r06_carry_mid_size.txt, alternating runs): gplus (87 MB) 19.9 -> 19.3 us, one rank's slab of mouse_gene split 2 ways (89 MB) 20.2 -> 19.4,
 // of hollywood split 8 ways (SWEEP, 113 MB) 24.6 -> 24.1, of ogbl-ppa split 2 ways (155 MB) 32.2 -> 31.4: carried up to 160 MiB.
 constexpr uint64_t kCarryMaxImageBytes = 160ull << 20;
 constexpr uint64_t kSlicedDeltaMaxImageBytes = 48ull << 20;   // the sliced DELTA plan of fixed-point dense layers (stream_tiles.cpp): measured up to 8.5 M non-zeros, no further
-constexpr uint64_t kResidentMaxImageBytes = 256ull << 20;   // SWEEP images up to the size of the Infinity Cache are streamed without the non-temporal hint (hs_api.cpp: stream_resident)
+constexpr uint64_t kResidentMaxImageBytes = 256ull << 20;   // SWEEP images up to the size of the Infinity Cache are streamed without the non-temporal hint (plan_stream_resident below)
 // Row-block (PAIRS / DELTA) images, round 6 (profiles/r06_rowblock_stream_policy*.txt): without `nt` where the image fits the Infinity Cache AND its blocks walk
 // several units.  Measured to gain a little even above the cache (ogbl-ppa, 267 MiB: -1.5 % warm) -- but an image that does not fit is evicted between
 // steps anyway, and once a caller alternates between matrices the cacheable policy COSTS: the headline matrix round-robin over three images ran 65.4 us per SpMV
@@ -122,6 +122,35 @@ constexpr uint64_t kDeltaMinSavedBytesFloat = 40u << 20;      // ... 6 us in the
 constexpr double kDenseMeanGap = 320.0;                       // DELTA blocks denser than this (>= 24 elements per row and sub-tile) sum per lane in registers (kBlockDenseRows);
                                                               // sparser ones lose with it (400000 x 100000, gap 512: 89.8 vs 83.2 us), denser ones win big (40000^2, gap 64: 34.5 vs 53.0)
 enum StreamFormat : uint32_t { kFormatPairs = 0, kFormatDelta = 1, kFormatBitmap = 2, kFormatOwner = 3, kFormatPairs24 = 4, kFormatOwner24 = 5, kFormatSweep = 6 };
+// The two plan-time decisions of a load that are not the planner's (hs_load.cpp; the options `stream_resident` / `carry_combine` = 0 | 1 decide otherwise).
+//
+// Stream residency.  SWEEP images that fit the 256 MiB Infinity Cache are streamed WITHOUT the non-temporal hint: repeated SpMVs of one matrix -- the
+// reference's benchmark loop, an iterative caller -- then read most of the image from the cache (profiles/r05_sweep_stream_policy.txt: one
+// rank's slab of ogbn-products split 8 ways, 124 MB: 39.5 -> 32.0 us; pokec, 247 MB: 61.1 -> 59.6-60.8 fixed, 69.3-70.3 -> 66.3-67.7 float_pob).
+// Larger images keep `nt` (a plain read loop over 1 GiB: 7.1 TB/s with it, 6.0 without: profiles/r02_hbm_read_bench.txt).
+// Round 6: the row-block kernels' PAIRS / DELTA streams too (spmv_kernels.hip: Ring<kRing | 4>), by their own rule (kRowblockResidentMaxImageBytes
+// above): up to the size of the cache where the blocks walk several units, tiny images whatever their shape; pure one-unit streams and everything
+// larger keep `nt` (hollywood: +13 % without it).  OWNER / OWNER24 / BITMAP / LIGHT images have no kernel without the hint: the decision is
+// taken for them by the SWEEP rule and has no effect (stream_policy_applies; hs_stats::stream_resident reports 0).
+constexpr bool rowblock_stream(uint32_t format, bool light) { return (format == kFormatPairs || format == kFormatDelta) && !light; }
+constexpr bool stream_policy_applies(uint32_t format, bool light) { return format == kFormatSweep || rowblock_stream(format, light); }
+constexpr bool plan_stream_resident(uint32_t format, bool light, uint64_t image_bytes, uint64_t num_units, uint64_t num_blocks) {
+    return rowblock_stream(format, light)
+               ? image_bytes <= kRowblockResidentMaxImageBytes && (num_units > num_blocks || image_bytes <= kRowblockResidentSmallImageBytes)
+               : image_bytes <= kResidentMaxImageBytes;
+}
+// The combine pass carried into the next step's kernel (hs_context.h: CarriedCombine), for plans of several column slices.
+// Measured (profiles/r05_carry_combine_ab.txt, three boxes, whole step): where a step is a few microseconds -- one rank's slab of
+// mouse_gene split 8 ways: 10.1 -> 8.6 us, the second launch WAS a third of it -- carrying wins every time.  On the large images it
+// is a wash that depends on the box and the run (ogbl-ppa 55.4 -> 53.5 / 54.2 / 57.0 us, hollywood 137.0 -> 135.1 / 139.1, the R-MAT
+// stand-in 60.0 -> 57.8 / 62.0, ogbn-products 206 -> 204; pokec's SWEEP kernel 73.5 -> 76.0: 33 MB of partial rows in front of every
+// launch): the partial rows a workgroup adds up were written by OTHER XCDs and come back from the memory side while nothing else of
+// the workgroup can start.  Hence: on by itself for images below 160 MiB (48 MiB until the middle was measured in round 6: kCarryMaxImageBytes
+// above), the launch-bound regime, and for OWNER / OWNER24 images of any size: ogbn-products gained 1-1.5 % in every one of four A/B pairs on
+// two boxes (profiles/r05_carry_combine_ab.txt) -- its workgroups run two blocks each and the carried rows ride on the first block's long prologue.
+constexpr bool plan_carries(uint32_t format, uint64_t image_bytes) {
+    return image_bytes < kCarryMaxImageBytes || format == kFormatOwner || format == kFormatOwner24;
+}
 // PAIRS24: PAIRS with a 24-bit position word -- 7 instead of 8 bytes per element.  A wavefront step is 448 bytes: 64 value dwords, then
 // 64 x 3 bytes (local_row << 13 | local_col, little endian), which the kernel reads as unaligned dwords at byte 256 + 3 * lane.
 // 11 bits of row: whenever no block has more than 2046 rows (nrows itself -- the spare accumulator -- must fit).  Opt-in

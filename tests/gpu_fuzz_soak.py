@@ -107,7 +107,7 @@ def run(n_cases=200, seed=1, profile=None, verbose=True):
                 bad = np.nonzero(got != want)[0] if impl == 0 else np.nonzero(~np.isclose(got.view(np.float32), want.view(np.float32), rtol=1e-4, atol=1e-4))[0]
                 bad_runs.append((r, len(bad), bad[:6].tolist()))
         # consecutive launches without anything in between: column-sliced plans carry the combine pass of one step into the next step's
-        # kernel (round 5, hs_api.cpp: enqueue / flush_combine) -- every burst length ends on either set of partial vectors
+        # kernel (round 5, hs_api.cpp: enqueue, hs_context.h: CarriedCombine) -- every burst length ends on either set of partial vectors
         for burst in (2, 3):
             for _ in range(burst):
                 eng.run()

@@ -1,4 +1,4 @@
-"""Column-sliced plans with carry_combine = 1 (round 5; hs_api.cpp: enqueue / flush_combine, spmv_device.h: CarriedCombine): when hs_run
+"""Column-sliced plans with carry_combine = 1 (round 5; hs_api.cpp: enqueue, hs_context.h: CarriedCombine on the host, spmv_device.h: CarriedCombine on the device): when hs_run
 follows hs_run the combine pass of the earlier step is done by the later step's kernel as its first act, and the stand-alone combine is
 launched only when something else follows.  Nothing observable may change: each scenario runs with carry_combine = 0 and = 1 and must give
 the same words, bit for bit (float modes too: the sums are taken in the same order)."""

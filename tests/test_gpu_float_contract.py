@@ -132,7 +132,7 @@ def test_spmm_routes_keep_the_bound(impl, monkeypatch):
         monkeypatch.delenv("HISPARSE_SPMM_MFMA")
         eng.set_option("spmm_fused", "0")
         Yloop = eng.spmm(X[:3])
-    # the route: hs_spmm takes the matrix engine for >= 5 float columns whenever the second image exists (hs_api.cpp, hs_spmm; asserted
+    # the route: hs_spmm takes the matrix engine for >= 5 float columns whenever the second image exists (hs_spmm.cpp, hs_spmm_device; asserted
     # above) -- and its words are not the fused kernel's: FMAs over unrounded products against fp32 batches summed in double
     assert not np.array_equal(Y16[:4], Y4)
     for j in range(16):

@@ -53,3 +53,29 @@ def test_reloads_do_not_leak_device_memory(monkeypatch):
                         eng.load_matrix_csr((3, 10, np.array([0, 2, 1, 3], dtype=np.uint32), np.array([4, 5, 1], dtype=np.uint32), np.ones(3, dtype=np.float32)))
     after = _free_bytes()
     assert before - after < (64 << 20), f"{(before - after) >> 20} MB of device memory did not come back"
+
+
+def test_reloading_a_tall_matrix_does_not_leak_its_row_map():
+    """One context, hs_load_matrix_csr of a tall hyper-sparse matrix 20 times over.  A load that plans by the tile census AND builds a
+    row-block image hands the device builder a row map (num_rows words, 9.6 MB here) twice; each upload must give the previous one back,
+    or every load loses that much (~190 MB over the 20)."""
+    rows = cols = 2_400_000
+    rng = np.random.default_rng(7)
+    third = cols // 3
+    indices = (rng.integers(0, third, size=(rows, 3), dtype=np.int64) + np.arange(3) * third).astype(np.uint32).ravel()   # three distinct, ascending columns per row
+    indptr = (np.arange(rows + 1, dtype=np.uint64) * 3).astype(np.uint32)
+    data = rng.uniform(0.5, 1.5, size=indices.size).astype(np.float32)
+    with device.SpmvEngine(0) as eng:
+        eng.set_option("stream_format", "pairs")                 # a row-block format: the builder's own pass over the row map is taken
+        eng.set_option("light", "0")
+        eng.load_matrix_csr((rows, cols, indptr, indices, data))     # the resident matrix, allocator pools: part of both readings
+        assert eng.stats()["retiled_on_gpu"] == 1
+        before = _free_bytes()
+        for _ in range(20):
+            eng.load_matrix_csr((rows, cols, indptr, indices, data))
+        after = _free_bytes()
+        eng.load_vector(host.pack_vector(0, np.ones(eng.num_cols, dtype=np.float32)))
+        eng.run()
+        y = eng.read_result()
+    assert before - after < (64 << 20), f"{(before - after) >> 20} MB of device memory did not come back"
+    assert np.count_nonzero(y) >= rows      # the last load is a working matrix

@@ -126,7 +126,7 @@ def test_more_than_eight_column_slices(impl, slices, monkeypatch):
 @pytest.mark.parametrize("impl", [0, 1, 2])
 @pytest.mark.parametrize("resident", ["0", "1"])
 def test_stream_policy_does_not_change_the_result(impl, resident, monkeypatch):
-    # SWEEP images that fit the Infinity Cache are streamed without the non-temporal hint (hs_api.cpp: stream_resident; its own instantiation
+    # SWEEP images that fit the Infinity Cache are streamed without the non-temporal hint (stream_tiles.h: plan_stream_resident; its own instantiation
     # of the kernel): both instantiations against the oracle, single launches and a burst
     monkeypatch.setenv("HISPARSE_SWEEP", "1")
     monkeypatch.setenv("HISPARSE_STREAM_RESIDENT", resident)
