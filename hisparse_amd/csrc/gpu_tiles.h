@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "device_buffer.h"
 #include "tiles_common.h"
 
 namespace hisparse {
@@ -37,7 +38,6 @@ class GpuTiler {
     // non-zero more during the load (`src`, the sorted CSR indices), 4 (+ 4 with a matrix-engine image) kept with the image.
     // Images of 16 GiB or more get no map (the word indices would not fit in 32 bits).
     GpuTiler(const detail::Layout& layout, const CsrView& csr, hipStream_t stream);
-    ~GpuTiler();
     GpuTiler(const GpuTiler&) = delete;
     GpuTiler& operator=(const GpuTiler&) = delete;
 
@@ -80,7 +80,7 @@ class GpuTiler {
     bool bitmap_emit(uint32_t slices, uint32_t groups_per_row, const std::vector<uint32_t>& range_of_row, const std::vector<BitmapBlock>& blocks,
                      const std::vector<uint64_t>& row_value_base, uint64_t image_bytes, uint64_t slack_bytes, const std::vector<BitmapRun>& runs,
                      std::vector<uint32_t>& run_prefix, std::vector<uint64_t>& run_heads, const MfmaImage* mfma, bool& duplicates);
-    uint8_t* release_mfma() { uint8_t* p = d_mfma_; d_mfma_ = nullptr; return p; }
+    uint8_t* release_mfma() { return d_mfma_.release(); }
     // ---- SWEEP (sweep_tiles.cpp plans: row ranges, column slices, the layout of streams and chunk-base tables; what touches every non-zero is here) ----
     // non-zeros per 128-byte line of x (32 columns): the slice boundaries are cut at equal modelled cost
     bool sweep_line_counts(uint32_t lines, std::vector<uint64_t>& line_nnz);
@@ -97,19 +97,27 @@ class GpuTiler {
     };
     bool sweep_emit(const std::vector<SweepBlock>& blocks, uint64_t image_bytes, uint64_t slack_bytes);
     // hands the device image over (hipFree by the new owner)
-    uint8_t* release_image() { uint8_t* p = d_image_; d_image_ = nullptr; return p; }
+    uint8_t* release_image() { return d_image_.release(); }
     // the value maps (csr.value_map; null when none was built): nnz words into the image / into the matrix-engine image
-    uint32_t* release_value_map() { uint32_t* p = d_map_; d_map_ = nullptr; return p; }
-    uint32_t* release_value_map2() { uint32_t* p = d_map2_; d_map2_ = nullptr; return p; }
+    uint32_t* release_value_map() { return d_map_.release(); }
+    uint32_t* release_value_map2() { return d_map2_.release(); }
 
   private:
     bool fail(const std::string& what);
     bool check(hipError_t e, const char* what);
     bool upload_channels();
     bool upload_csr(std::vector<uint32_t>& row_nnz);
-    bool decode_error(const char* pass);
+    // the error words of the element passes, read back (`copy` / `sync`: what a HIP failure of either step is reported as); false + error():
+    // a lane stream (CPSR source) or a CSR row holds an element outside the matrix
+    bool read_error(const char* copy, const char* sync);
     bool gather_values();
-    bool alloc_map(uint32_t** map, uint64_t image_bytes);
+    void release_source();
+    bool alloc_map(DeviceBuffer<uint32_t>& map, uint64_t image_bytes);
+    // What the element passes read, as the kernels take it, and one thread per piece of it.  (Templates because the kernels' parameter types
+    // -- gpu_tiles.hip: ElementSource, StreamGroup -- are local to that file and name its kernels' symbols: S and G are always those two.)
+    template <typename S> S source() const;
+    template <typename G> const G* groups() const { return reinterpret_cast<const G*>(d_groups_.get()); }
+    uint64_t element_threads() const;
 
     detail::Layout L_;
     Geometry geom_;
@@ -119,27 +127,27 @@ class GpuTiler {
     std::string error_;
 
     const CsrView* csr_ = nullptr;         // CSR source (then channel_ / n_packets_ are null)
-    uint32_t* d_indptr_ = nullptr;         // CSR source: indptr of the PADDED matrix (num_rows + 1), indices, values
-    uint32_t* d_indices_ = nullptr;
-    float* d_values_ = nullptr;
-    uint8_t* d_channels_ = nullptr;        // the 16 channel buffers back to back
-    void* d_groups_ = nullptr;             // StreamGroup[num_groups_]: the 8 lane streams of one (partition, virtual channel)
+    DeviceBuffer<uint32_t> d_indptr_;      // CSR source: indptr of the PADDED matrix (num_rows + 1), indices, values
+    DeviceBuffer<uint32_t> d_indices_;
+    DeviceBuffer<float> d_values_;
+    DeviceBuffer<uint8_t> d_channels_;     // the 16 channel buffers back to back
+    DeviceBuffer<uint8_t> d_groups_;       // StreamGroup[num_groups_]: the 8 lane streams of one (partition, virtual channel)
     uint32_t num_groups_ = 0;
     uint32_t total_slots_ = 0;             // segments of all lane streams (gpu_tiles.hip: kSegment entries each)
-    uint64_t* d_advance_ = nullptr;        // per segment: marker counts in front of it (exclusive scan)
-    uint64_t* d_base_ = nullptr;           // per segment: non-zeros in front of it (exclusive scan; [total_slots_] = all)
-    uint32_t* d_scalar_ = nullptr;         // error / flag words
-    uint32_t* d_block_of_row_ = nullptr;
+    DeviceBuffer<uint64_t> d_advance_;     // per segment: marker counts in front of it (exclusive scan)
+    DeviceBuffer<uint64_t> d_base_;        // per segment: non-zeros in front of it (exclusive scan; [total_slots_] = all)
+    DeviceBuffer<uint32_t> d_scalar_;      // error / flag words
+    DeviceBuffer<uint32_t> d_block_of_row_;
     uint64_t total_ = 0;                   // non-zeros
-    uint64_t* d_keys_ = nullptr;           // sorted: unit << 28 | position
-    uint32_t* d_vals_ = nullptr;           // sorted value words
-    uint64_t* d_bridges_ = nullptr;        // DELTA: inclusive scan of the bridge slots in front of every element
-    uint8_t* d_image_ = nullptr;
-    uint8_t* d_mfma_ = nullptr;            // BITMAP, float modes: the matrix-engine image (stream_tiles.h: MfmaImage)
+    DeviceBuffer<uint64_t> d_keys_;        // sorted: unit << 28 | position
+    DeviceBuffer<uint32_t> d_vals_;        // sorted value words
+    DeviceBuffer<uint64_t> d_bridges_;     // DELTA: inclusive scan of the bridge slots in front of every element
+    DeviceBuffer<uint8_t> d_image_;
+    DeviceBuffer<uint8_t> d_mfma_;         // BITMAP, float modes: the matrix-engine image (stream_tiles.h: MfmaImage)
     bool value_map_ = false;               // CSR source with csr.value_map: build the value maps
-    uint32_t* d_src_ = nullptr;            // value map, element formats: CSR index of every sorted element (beside d_vals_)
-    uint32_t* d_map_ = nullptr;            // value map: word index into the image of every non-zero, CSR order
-    uint32_t* d_map2_ = nullptr;           // value map: word index into the matrix-engine image
+    DeviceBuffer<uint32_t> d_src_;         // value map, element formats: CSR index of every sorted element (beside d_vals_)
+    DeviceBuffer<uint32_t> d_map_;         // value map: word index into the image of every non-zero, CSR order
+    DeviceBuffer<uint32_t> d_map2_;        // value map: word index into the matrix-engine image
 };
 
 }  // namespace dev

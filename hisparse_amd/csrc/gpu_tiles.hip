@@ -642,11 +642,12 @@ __global__ __launch_bounds__(256) void mfma_values_kernel(ElementSource src, uin
     });
 }
 
-template <typename T>
-hipError_t upload(T** dst, const std::vector<T>& src, hipStream_t stream) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), std::max<size_t>(src.size() * sizeof(T), 16));
+template <typename T, typename U>
+hipError_t upload(DeviceBuffer<T>& dst, const std::vector<U>& src, hipStream_t stream) {
+    static_assert(std::is_same_v<T, U> || sizeof(T) == 1, "a buffer of its own type, or of bytes (the group table)");
+    hipError_t e = dst.alloc(std::max<size_t>(src.size() * sizeof(U), 16));
     if (e != hipSuccess || src.empty()) return e;
-    return hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, stream);
+    return hipMemcpyAsync(dst.get(), src.data(), src.size() * sizeof(U), hipMemcpyHostToDevice, stream);
 }
 
 }  // namespace
@@ -665,15 +666,6 @@ GpuTiler::GpuTiler(const Layout& layout, const void* const channel[NUM_HBM_CHANN
 GpuTiler::GpuTiler(const Layout& layout, const CsrView& csr, hipStream_t stream)
     : L_(layout), geom_(*layout.g), channel_(nullptr), n_packets_(nullptr), stream_(stream), csr_(&csr), value_map_(csr.value_map) {
     L_.g = &geom_;
-}
-
-GpuTiler::~GpuTiler() {
-    for (void* p : {static_cast<void*>(d_indptr_), static_cast<void*>(d_indices_), static_cast<void*>(d_values_)})
-        if (p) (void)hipFree(p);
-    for (void* p : {static_cast<void*>(d_channels_), d_groups_, static_cast<void*>(d_advance_), static_cast<void*>(d_base_), static_cast<void*>(d_scalar_),
-                    static_cast<void*>(d_block_of_row_), static_cast<void*>(d_keys_), static_cast<void*>(d_vals_), static_cast<void*>(d_bridges_),
-                    static_cast<void*>(d_image_), static_cast<void*>(d_mfma_), static_cast<void*>(d_src_), static_cast<void*>(d_map_), static_cast<void*>(d_map2_)})
-        if (p) (void)hipFree(p);
 }
 
 bool GpuTiler::fail(const std::string& what) {
@@ -735,26 +727,33 @@ bool GpuTiler::upload_channels() {
     if (slots >= (uint64_t(1) << 32)) return fail("gpu re-tile: image too large for 32-bit segment indices");
     num_groups_ = uint32_t(groups.size());
     total_slots_ = uint32_t(slots);
-    if (!check(hipMalloc(reinterpret_cast<void**>(&d_channels_), std::max<uint64_t>(total, 64)), "hipMalloc(channels)")) return false;
+    if (!check(d_channels_.alloc_count(total, 64), "hipMalloc(channels)")) return false;
     for (uint32_t pc = 0; pc < NUM_HBM_CHANNELS; ++pc)
         if (n_packets_[pc] &&
-            !check(hipMemcpyAsync(d_channels_ + offset[pc], channel_[pc], n_packets_[pc] * sizeof(MatPkt), hipMemcpyHostToDevice, stream_), "upload channel"))
+            !check(hipMemcpyAsync(d_channels_.get() + offset[pc], channel_[pc], n_packets_[pc] * sizeof(MatPkt), hipMemcpyHostToDevice, stream_), "upload channel"))
             return false;
-    StreamGroup* d = nullptr;
-    if (!check(upload(&d, groups, stream_), "upload stream groups")) return false;
-    d_groups_ = d;
-    if (!check(hipMalloc(reinterpret_cast<void**>(&d_scalar_), 64), "hipMalloc")) return false;
-    if (!check(hipMemsetAsync(d_scalar_, 0, 64, stream_), "hipMemset")) return false;
+    if (!check(upload(d_groups_, groups, stream_), "upload stream groups")) return false;
+    if (!check(d_scalar_.alloc(64), "hipMalloc")) return false;
+    if (!check(hipMemsetAsync(d_scalar_.get(), 0, 64, stream_), "hipMemset")) return false;
     return check(hipStreamSynchronize(stream_), "upload");       // the group table is a temporary
 }
 
-bool GpuTiler::decode_error(const char* pass) {
+template <typename S>
+S GpuTiler::source() const {
+    return S{d_channels_.get(), groups<StreamGroup>(), d_advance_.get(), d_indptr_.get(), d_indices_.get(), d_values_.get(), total_, num_groups_, total_slots_,
+             L_.num_rows, csr_ ? csr_->num_cols : L_.num_cols, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), csr_ ? 1u : 0u};
+}
+uint64_t GpuTiler::element_threads() const { return csr_ ? (total_ + kCsrSegment - 1) / kCsrSegment : total_slots_; }
+
+bool GpuTiler::read_error(const char* copy, const char* sync) {
     uint32_t words[3] = {0, 0, 0};
-    if (!check(hipMemcpyAsync(words, d_scalar_, 12, hipMemcpyDeviceToHost, stream_), pass)) return false;
-    if (!check(hipStreamSynchronize(stream_), pass)) return false;
+    if (!check(hipMemcpyAsync(words, d_scalar_.get(), 12, hipMemcpyDeviceToHost, stream_), copy)) return false;
+    if (!check(hipStreamSynchronize(stream_), sync)) return false;
     if (!words[0]) return true;
+    const std::string at = std::to_string(uint64_t(words[1]) * PACK_SIZE + words[2]);
+    if (csr_) return fail("CSR row " + at + ": column index outside the matrix");
     // which stream: for the message only (the host walk names channel / partitions too)
-    return fail(std::string("lane stream ") + std::to_string(uint64_t(words[1]) * PACK_SIZE + words[2]) + ": " +
+    return fail("lane stream " + at + ": " +
                 (words[0] == kErrColumn ? "column index outside the column partition" : "decoded row outside the row partition (marker count wrapped?)"));
 }
 
@@ -771,28 +770,28 @@ bool GpuTiler::upload_csr(std::vector<uint32_t>& row_nnz) {
     std::vector<uint32_t> indptr(size_t(L_.num_rows) + 1, uint32_t(total_));
     for (uint32_t r = 0; r < m.num_rows; ++r) { indptr[r] = m.indptr[r]; row_nnz[r] = m.indptr[r + 1] - m.indptr[r]; }
     const size_t n = std::max<uint64_t>(total_, 1);
-    bool ok = check(upload(&d_indptr_, indptr, stream_), "upload indptr") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_indices_), n * 4), "hipMalloc(indices)") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_values_), n * 4), "hipMalloc(values)") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_scalar_), 64), "hipMalloc") && check(hipMemsetAsync(d_scalar_, 0, 64, stream_), "hipMemset");
+    bool ok = check(upload(d_indptr_, indptr, stream_), "upload indptr") && check(d_indices_.alloc_count(n), "hipMalloc(indices)") &&
+              check(d_values_.alloc_count(n), "hipMalloc(values)") && check(d_scalar_.alloc(64), "hipMalloc") &&
+              check(hipMemsetAsync(d_scalar_.get(), 0, 64, stream_), "hipMemset");
     if (ok && total_)
-        ok = check(hipMemcpyAsync(d_indices_, m.indices, size_t(total_) * 4, hipMemcpyHostToDevice, stream_), "upload indices") &&
-             check(hipMemcpyAsync(d_values_, m.values, size_t(total_) * 4, hipMemcpyHostToDevice, stream_), "upload values");
+        ok = check(hipMemcpyAsync(d_indices_.get(), m.indices, size_t(total_) * 4, hipMemcpyHostToDevice, stream_), "upload indices") &&
+             check(hipMemcpyAsync(d_values_.get(), m.values, size_t(total_) * 4, hipMemcpyHostToDevice, stream_), "upload values");
     return ok && check(hipStreamSynchronize(stream_), "upload");      // `indptr` is a temporary
 }
 
 // value map: the sorted payload (d_vals_) holds CSR indices -- move them to d_src_ and make the value words from the CSR values
 bool GpuTiler::gather_values() {
-    if (!check(hipMalloc(reinterpret_cast<void**>(&d_src_), std::max<uint64_t>(total_, 1) * 4), "hipMalloc(value map sources)")) return false;
-    hipLaunchKernelGGL(map_gather_kernel, dim3(uint32_t((total_ + 255) / 256)), dim3(256), 0, stream_, d_values_, uint32_t(geom_.impl == IMPL_FIXED), total_, d_vals_, d_src_);
+    if (!check(d_src_.alloc_count(std::max<uint64_t>(total_, 1)), "hipMalloc(value map sources)")) return false;
+    hipLaunchKernelGGL(map_gather_kernel, dim3(uint32_t((total_ + 255) / 256)), dim3(256), 0, stream_, d_values_.get(), uint32_t(geom_.impl == IMPL_FIXED), total_,
+                       d_vals_.get(), d_src_.get());
     return check(hipGetLastError(), "map_gather_kernel");
 }
 
 // value map: a map of `total_` words, 0xffffffff (no entry) until the emit kernels fill it; false = the image is too large for one
-bool GpuTiler::alloc_map(uint32_t** map, uint64_t image_bytes) {
+bool GpuTiler::alloc_map(DeviceBuffer<uint32_t>& map, uint64_t image_bytes) {
     if (image_bytes / 4 >= kMapMaxWords) return true;
     const size_t bytes = std::max<uint64_t>(total_, 1) * 4;
-    return check(hipMalloc(reinterpret_cast<void**>(map), bytes), "hipMalloc(value map)") && check(hipMemsetAsync(*map, 0xff, bytes, stream_), "hipMemset(value map)");
+    return check(map.alloc(bytes), "hipMalloc(value map)") && check(hipMemsetAsync(map.get(), 0xff, bytes, stream_), "hipMemset(value map)");
 }
 
 bool GpuTiler::count_rows(std::vector<uint32_t>& row_nnz, uint64_t& nnz) {
@@ -805,43 +804,43 @@ bool GpuTiler::count_rows(std::vector<uint32_t>& row_nnz, uint64_t& nnz) {
     }
     if (!upload_channels()) return false;
     timer.lap("gpu: upload CPSR image");
-    const StreamGroup* groups = static_cast<const StreamGroup*>(d_groups_);
+    const StreamGroup* groups = this->groups<StreamGroup>();
     const size_t slots = size_t(total_slots_) + 1;                   // + one zero: the exclusive scans end with the totals
     const dim3 grid((total_slots_ + 255) / 256), block(256);
-    uint32_t* d_rows = nullptr;
-    uint64_t *d_adv_in = nullptr, *d_cnt_in = nullptr;
-    void* d_temp = nullptr;
-    size_t temp_bytes = 0;
-    bool ok = check(hipMalloc(reinterpret_cast<void**>(&d_rows), std::max<size_t>(size_t(L_.num_rows) * 4, 16)), "hipMalloc") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_adv_in), slots * 8), "hipMalloc") && check(hipMalloc(reinterpret_cast<void**>(&d_cnt_in), slots * 8), "hipMalloc") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_advance_), slots * 8), "hipMalloc") && check(hipMalloc(reinterpret_cast<void**>(&d_base_), slots * 8), "hipMalloc") &&
-              check(hipMemsetAsync(d_rows, 0, size_t(L_.num_rows) * 4, stream_), "hipMemset") &&
-              check(hipMemsetAsync(d_adv_in + total_slots_, 0, 8, stream_), "hipMemset") && check(hipMemsetAsync(d_cnt_in + total_slots_, 0, 8, stream_), "hipMemset") &&
-              check(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_adv_in, d_advance_, slots, stream_), "scan (size)") &&
-              check(hipMalloc(&d_temp, std::max<size_t>(temp_bytes, 16)), "hipMalloc(scan)");
     auto lap = [&](const char* what) { if (timer.on) { (void)hipStreamSynchronize(stream_); timer.lap(what); } };
-    lap("gpu:   allocations");
-    if (ok && total_slots_) {
-        hipLaunchKernelGGL(segment_sums_kernel, grid, block, 0, stream_, d_channels_, groups, num_groups_, total_slots_, d_adv_in, d_cnt_in);
-        ok = check(hipGetLastError(), "segment_sums_kernel");
-    }
-    lap("gpu:   segment sums");
-    ok = ok && check(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_adv_in, d_advance_, slots, stream_), "scan") &&
-         check(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_cnt_in, d_base_, slots, stream_), "scan");
-    lap("gpu:   scans");
-    if (ok && total_slots_) {
-        hipLaunchKernelGGL(count_rows_kernel, grid, block, 0, stream_, d_channels_, groups, num_groups_, total_slots_, d_advance_, d_rows, d_scalar_);
-        ok = check(hipGetLastError(), "count_rows_kernel") && decode_error("count rows");
-    }
-    lap("gpu:   row counts");
-    row_nnz.assign(L_.num_rows, 0);
+    bool ok;
     uint64_t all = 0;
-    ok = ok && (L_.num_rows == 0 || check(hipMemcpyAsync(row_nnz.data(), d_rows, size_t(L_.num_rows) * 4, hipMemcpyDeviceToHost, stream_), "read row counts")) &&
-         check(hipMemcpyAsync(&all, d_base_ + total_slots_, 8, hipMemcpyDeviceToHost, stream_), "read total") &&
-         check(hipStreamSynchronize(stream_), "count rows");
-    lap("gpu:   read back");
-    for (void* p : {static_cast<void*>(d_rows), static_cast<void*>(d_adv_in), static_cast<void*>(d_cnt_in), d_temp})
-        if (p) (void)hipFree(p);
+    {
+        DeviceBuffer<uint32_t> d_rows;
+        DeviceBuffer<uint64_t> d_adv_in, d_cnt_in;
+        DeviceBuffer<uint8_t> d_temp;
+        size_t temp_bytes = 0;
+        ok = check(d_rows.alloc_count(L_.num_rows, 16), "hipMalloc") && check(d_adv_in.alloc_count(slots), "hipMalloc") && check(d_cnt_in.alloc_count(slots), "hipMalloc") &&
+             check(d_advance_.alloc_count(slots), "hipMalloc") && check(d_base_.alloc_count(slots), "hipMalloc") &&
+             check(hipMemsetAsync(d_rows.get(), 0, size_t(L_.num_rows) * 4, stream_), "hipMemset") &&
+             check(hipMemsetAsync(d_adv_in.get() + total_slots_, 0, 8, stream_), "hipMemset") && check(hipMemsetAsync(d_cnt_in.get() + total_slots_, 0, 8, stream_), "hipMemset") &&
+             check(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_adv_in.get(), d_advance_.get(), slots, stream_), "scan (size)") &&
+             check(d_temp.alloc_count(temp_bytes, 16), "hipMalloc(scan)");
+        lap("gpu:   allocations");
+        if (ok && total_slots_) {
+            hipLaunchKernelGGL(segment_sums_kernel, grid, block, 0, stream_, d_channels_.get(), groups, num_groups_, total_slots_, d_adv_in.get(), d_cnt_in.get());
+            ok = check(hipGetLastError(), "segment_sums_kernel");
+        }
+        lap("gpu:   segment sums");
+        ok = ok && check(hipcub::DeviceScan::ExclusiveSum(d_temp.get(), temp_bytes, d_adv_in.get(), d_advance_.get(), slots, stream_), "scan") &&
+             check(hipcub::DeviceScan::ExclusiveSum(d_temp.get(), temp_bytes, d_cnt_in.get(), d_base_.get(), slots, stream_), "scan");
+        lap("gpu:   scans");
+        if (ok && total_slots_) {
+            hipLaunchKernelGGL(count_rows_kernel, grid, block, 0, stream_, d_channels_.get(), groups, num_groups_, total_slots_, d_advance_.get(), d_rows.get(), d_scalar_.get());
+            ok = check(hipGetLastError(), "count_rows_kernel") && read_error("count rows", "count rows");
+        }
+        lap("gpu:   row counts");
+        row_nnz.assign(L_.num_rows, 0);
+        ok = ok && (L_.num_rows == 0 || check(hipMemcpyAsync(row_nnz.data(), d_rows.get(), size_t(L_.num_rows) * 4, hipMemcpyDeviceToHost, stream_), "read row counts")) &&
+             check(hipMemcpyAsync(&all, d_base_.get() + total_slots_, 8, hipMemcpyDeviceToHost, stream_), "read total") &&
+             check(hipStreamSynchronize(stream_), "count rows");
+        lap("gpu:   read back");
+    }      // (the temporaries go back here)
     lap("gpu:   frees");
     total_ = nnz = all;
     timer.lap("gpu: segment scan + row counts");
@@ -851,31 +850,22 @@ bool GpuTiler::count_rows(std::vector<uint32_t>& row_nnz, uint64_t& nnz) {
 bool GpuTiler::count_tiles(const std::vector<uint32_t>& block_of_row, uint32_t num_ranges, std::vector<uint32_t>& cnt) {
     const uint32_t S = L_.subs_per_cp, tiles = L_.col_parts * S;
     cnt.assign(size_t(num_ranges) * tiles, 0);
-    uint32_t* d_cnt = nullptr;
-    if (d_block_of_row_) (void)hipFree(d_block_of_row_);      // (a load calls this twice: the census's row map, then the plan's)
-    d_block_of_row_ = nullptr;
-    if (!check(upload(&d_block_of_row_, block_of_row, stream_), "upload block_of_row")) return false;
-    if (!check(hipMalloc(reinterpret_cast<void**>(&d_cnt), std::max<size_t>(cnt.size() * 4, 16)), "hipMalloc")) return false;
-    bool ok = check(hipMemsetAsync(d_cnt, 0, cnt.size() * 4, stream_), "hipMemset");
+    DeviceBuffer<uint32_t> d_cnt;
+    // (a load calls this twice: the census's row map, then the plan's -- the upload gives the previous one back first)
+    if (!check(upload(d_block_of_row_, block_of_row, stream_), "upload block_of_row")) return false;
+    if (!check(d_cnt.alloc_count(cnt.size(), 16), "hipMalloc")) return false;
+    bool ok = check(hipMemsetAsync(d_cnt.get(), 0, cnt.size() * 4, stream_), "hipMemset");
     if (ok && csr_ && total_) {
-        const uint64_t threads = (total_ + kCsrSegment - 1) / kCsrSegment;
-        hipLaunchKernelGGL(csr_count_tiles_kernel, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, d_indptr_, d_indices_, L_.num_rows, total_,
-                           csr_->num_cols, uint32_t(geom_.logical_vb), d_block_of_row_, tiles, S, L_.sub_width, d_cnt, d_scalar_);
-        ok = check(hipGetLastError(), "csr_count_tiles_kernel");
-        if (ok) {
-            uint32_t words[3] = {0, 0, 0};
-            ok = check(hipMemcpyAsync(words, d_scalar_, 12, hipMemcpyDeviceToHost, stream_), "count tiles") && check(hipStreamSynchronize(stream_), "count tiles");
-            if (ok && words[0]) ok = fail("CSR row " + std::to_string(uint64_t(words[1]) * PACK_SIZE + words[2]) + ": column index outside the matrix");
-        }
+        hipLaunchKernelGGL(csr_count_tiles_kernel, dim3(uint32_t((element_threads() + 255) / 256)), dim3(256), 0, stream_, d_indptr_.get(), d_indices_.get(), L_.num_rows,
+                           total_, csr_->num_cols, uint32_t(geom_.logical_vb), d_block_of_row_.get(), tiles, S, L_.sub_width, d_cnt.get(), d_scalar_.get());
+        ok = check(hipGetLastError(), "csr_count_tiles_kernel") && read_error("count tiles", "count tiles");
     } else if (ok && total_slots_) {
-        hipLaunchKernelGGL(count_tiles_kernel, dim3((total_slots_ + 255) / 256), dim3(256), 0, stream_, d_channels_, static_cast<const StreamGroup*>(d_groups_),
-                           num_groups_, total_slots_, d_advance_, d_block_of_row_, tiles, S, L_.sub_width, d_cnt);
+        hipLaunchKernelGGL(count_tiles_kernel, dim3((total_slots_ + 255) / 256), dim3(256), 0, stream_, d_channels_.get(), groups<StreamGroup>(), num_groups_, total_slots_,
+                           d_advance_.get(), d_block_of_row_.get(), tiles, S, L_.sub_width, d_cnt.get());
         ok = check(hipGetLastError(), "count_tiles_kernel");
     }
-    ok = ok && (cnt.empty() || check(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * 4, hipMemcpyDeviceToHost, stream_), "read tile counts")) &&
-         check(hipStreamSynchronize(stream_), "count tiles");
-    (void)hipFree(d_cnt);
-    return ok;
+    return ok && (cnt.empty() || check(hipMemcpyAsync(cnt.data(), d_cnt.get(), cnt.size() * 4, hipMemcpyDeviceToHost, stream_), "read tile counts")) &&
+           check(hipStreamSynchronize(stream_), "count tiles");
 }
 
 bool GpuTiler::sort_elements(const std::vector<uint32_t>& block_of_row, const std::vector<uint32_t>& range_row0, const std::vector<uint32_t>& unit_of,
@@ -884,24 +874,21 @@ bool GpuTiler::sort_elements(const std::vector<uint32_t>& block_of_row, const st
     detail::PhaseTimer timer;
     duplicates = false;
     const uint32_t S = L_.subs_per_cp, tiles = L_.col_parts * S;
-    uint32_t *d_row0 = nullptr, *d_unit_of = nullptr, *d_vals_in = nullptr;
-    uint64_t* d_keys_in = nullptr;
-    void* d_temp = nullptr;
+    DeviceBuffer<uint32_t> d_row0, d_unit_of, d_vals_in;
+    DeviceBuffer<uint64_t> d_keys_in;
+    DeviceBuffer<uint8_t> d_temp;
     const size_t n = std::max<uint64_t>(total_, 1);
-    bool ok = check(upload(&d_row0, range_row0, stream_), "upload range rows") && check(upload(&d_unit_of, unit_of, stream_), "upload unit table") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_keys_in), n * 8), "hipMalloc(keys)") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_vals_in), n * 4), "hipMalloc(values)") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_keys_), n * 8), "hipMalloc(keys)") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_vals_), n * 4), "hipMalloc(values)");
+    bool ok = check(upload(d_row0, range_row0, stream_), "upload range rows") && check(upload(d_unit_of, unit_of, stream_), "upload unit table") &&
+              check(d_keys_in.alloc_count(n), "hipMalloc(keys)") && check(d_vals_in.alloc_count(n), "hipMalloc(values)") &&
+              check(d_keys_.alloc_count(n), "hipMalloc(keys)") && check(d_vals_.alloc_count(n), "hipMalloc(values)");
     if (ok && csr_ && total_) {
-        const uint64_t threads = (total_ + kCsrSegment - 1) / kCsrSegment;
-        hipLaunchKernelGGL(value_map_ ? csr_keys_kernel<true> : csr_keys_kernel<false>, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, d_indptr_,
-                           d_indices_, d_values_, L_.num_rows, total_, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), d_block_of_row_, d_row0,
-                           d_unit_of, tiles, S, L_.sub_width, d_keys_in, d_vals_in);
+        hipLaunchKernelGGL(value_map_ ? csr_keys_kernel<true> : csr_keys_kernel<false>, dim3(uint32_t((element_threads() + 255) / 256)), dim3(256), 0, stream_,
+                           d_indptr_.get(), d_indices_.get(), d_values_.get(), L_.num_rows, total_, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED),
+                           d_block_of_row_.get(), d_row0.get(), d_unit_of.get(), tiles, S, L_.sub_width, d_keys_in.get(), d_vals_in.get());
         ok = check(hipGetLastError(), "csr_keys_kernel");
     } else if (ok && total_slots_) {
-        hipLaunchKernelGGL(keys_kernel, dim3((total_slots_ + 255) / 256), dim3(256), 0, stream_, d_channels_, static_cast<const StreamGroup*>(d_groups_),
-                           num_groups_, total_slots_, d_advance_, d_base_, d_block_of_row_, d_row0, d_unit_of, tiles, S, L_.sub_width, d_keys_in, d_vals_in);
+        hipLaunchKernelGGL(keys_kernel, dim3((total_slots_ + 255) / 256), dim3(256), 0, stream_, d_channels_.get(), groups<StreamGroup>(), num_groups_, total_slots_,
+                           d_advance_.get(), d_base_.get(), d_block_of_row_.get(), d_row0.get(), d_unit_of.get(), tiles, S, L_.sub_width, d_keys_in.get(), d_vals_in.get());
         ok = check(hipGetLastError(), "keys_kernel");
     }
     if (timer.on) { (void)hipStreamSynchronize(stream_); timer.lap("gpu: keys"); }
@@ -910,27 +897,30 @@ bool GpuTiler::sort_elements(const std::vector<uint32_t>& block_of_row, const st
         while ((uint64_t(1) << unit_bits) < plans.size() + 1) ++unit_bits;
         const int end_bit = int(kPosBits + unit_bits);
         size_t temp_bytes = 0;
-        ok = check(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys_in, d_keys_, d_vals_in, d_vals_, total_, 0, end_bit, stream_), "radix sort (size)") &&
-             check(hipMalloc(&d_temp, std::max<size_t>(temp_bytes, 16)), "hipMalloc(sort)") &&
-             check(hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, d_keys_in, d_keys_, d_vals_in, d_vals_, total_, 0, end_bit, stream_), "radix sort");
+        ok = check(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys_in.get(), d_keys_.get(), d_vals_in.get(), d_vals_.get(), total_, 0, end_bit, stream_), "radix sort (size)") &&
+             check(d_temp.alloc_count(temp_bytes, 16), "hipMalloc(sort)") &&
+             check(hipcub::DeviceRadixSort::SortPairs(d_temp.get(), temp_bytes, d_keys_in.get(), d_keys_.get(), d_vals_in.get(), d_vals_.get(), total_, 0, end_bit, stream_), "radix sort");
         if (ok && value_map_) ok = gather_values();
         if (ok) {
-            (void)hipMemsetAsync(d_scalar_ + 4, 0, 4, stream_);
-            hipLaunchKernelGGL(duplicates_kernel, dim3(uint32_t((total_ + 255) / 256)), dim3(256), 0, stream_, d_keys_, total_, d_scalar_ + 4);
+            (void)hipMemsetAsync(d_scalar_.get() + 4, 0, 4, stream_);
+            hipLaunchKernelGGL(duplicates_kernel, dim3(uint32_t((total_ + 255) / 256)), dim3(256), 0, stream_, d_keys_.get(), total_, d_scalar_.get() + 4);
             uint32_t flag = 0;
-            ok = check(hipMemcpyAsync(&flag, d_scalar_ + 4, 4, hipMemcpyDeviceToHost, stream_), "duplicates") && check(hipStreamSynchronize(stream_), "sort");
+            ok = check(hipMemcpyAsync(&flag, d_scalar_.get() + 4, 4, hipMemcpyDeviceToHost, stream_), "duplicates") && check(hipStreamSynchronize(stream_), "sort");
             duplicates = flag != 0;
         }
     }
     ok = ok && check(hipStreamSynchronize(stream_), "sort");
     timer.lap("gpu: radix sort");
-    for (void* p : {static_cast<void*>(d_row0), static_cast<void*>(d_unit_of), static_cast<void*>(d_keys_in), static_cast<void*>(d_vals_in), d_temp})
-        if (p) (void)hipFree(p);
-    // the source is not needed any more
-    if (d_channels_) { (void)hipFree(d_channels_); d_channels_ = nullptr; }
-    for (void** p : {reinterpret_cast<void**>(&d_indptr_), reinterpret_cast<void**>(&d_indices_), reinterpret_cast<void**>(&d_values_)})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    release_source();
     return ok;
+}
+
+// the source is not needed any more
+void GpuTiler::release_source() {
+    d_channels_.reset();
+    d_indptr_.reset();
+    d_indices_.reset();
+    d_values_.reset();
 }
 
 namespace {
@@ -958,30 +948,28 @@ bool make_device_plans(const std::vector<UnitPlan>& plans, const std::vector<uin
 
 bool GpuTiler::delta_slots(std::vector<UnitPlan>& plans) {
     const size_t n = std::max<uint64_t>(total_, 1);
-    uint64_t *d_in = nullptr, *d_slots = nullptr;
-    DevicePlan* d_plans = nullptr;
-    void* d_temp = nullptr;
+    DeviceBuffer<uint64_t> d_in, d_slots;
+    DeviceBuffer<DevicePlan> d_plans;
+    DeviceBuffer<uint8_t> d_temp;
     std::vector<DevicePlan> dp;
     make_device_plans(plans, {}, {}, dp);
-    bool ok = check(hipMalloc(reinterpret_cast<void**>(&d_in), n * 8), "hipMalloc") && check(hipMalloc(reinterpret_cast<void**>(&d_bridges_), n * 8), "hipMalloc") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_slots), std::max<size_t>(plans.size() * 8, 16)), "hipMalloc") && check(upload(&d_plans, dp, stream_), "upload plans");
+    bool ok = check(d_in.alloc_count(n), "hipMalloc") && check(d_bridges_.alloc_count(n), "hipMalloc") && check(d_slots.alloc_count(plans.size(), 16), "hipMalloc") &&
+              check(upload(d_plans, dp, stream_), "upload plans");
     if (ok && total_) {
-        hipLaunchKernelGGL(bridges_kernel, dim3(uint32_t((total_ + 255) / 256)), dim3(256), 0, stream_, d_keys_, total_, d_in);
+        hipLaunchKernelGGL(bridges_kernel, dim3(uint32_t((total_ + 255) / 256)), dim3(256), 0, stream_, d_keys_.get(), total_, d_in.get());
         size_t temp_bytes = 0;
         ok = check(hipGetLastError(), "bridges_kernel") &&
-             check(hipcub::DeviceScan::InclusiveSum(nullptr, temp_bytes, d_in, d_bridges_, total_, stream_), "scan (size)") &&
-             check(hipMalloc(&d_temp, std::max<size_t>(temp_bytes, 16)), "hipMalloc(scan)") &&
-             check(hipcub::DeviceScan::InclusiveSum(d_temp, temp_bytes, d_in, d_bridges_, total_, stream_), "scan");
+             check(hipcub::DeviceScan::InclusiveSum(nullptr, temp_bytes, d_in.get(), d_bridges_.get(), total_, stream_), "scan (size)") &&
+             check(d_temp.alloc_count(temp_bytes, 16), "hipMalloc(scan)") &&
+             check(hipcub::DeviceScan::InclusiveSum(d_temp.get(), temp_bytes, d_in.get(), d_bridges_.get(), total_, stream_), "scan");
     }
     std::vector<uint64_t> slots(plans.size(), 0);
     if (ok && !plans.empty()) {
-        hipLaunchKernelGGL(unit_slots_kernel, dim3(uint32_t((plans.size() + 255) / 256)), dim3(256), 0, stream_, d_plans, uint32_t(plans.size()), d_bridges_, d_slots);
+        hipLaunchKernelGGL(unit_slots_kernel, dim3(uint32_t((plans.size() + 255) / 256)), dim3(256), 0, stream_, d_plans.get(), uint32_t(plans.size()), d_bridges_.get(), d_slots.get());
         ok = check(hipGetLastError(), "unit_slots_kernel") &&
-             check(hipMemcpyAsync(slots.data(), d_slots, slots.size() * 8, hipMemcpyDeviceToHost, stream_), "read slots");
+             check(hipMemcpyAsync(slots.data(), d_slots.get(), slots.size() * 8, hipMemcpyDeviceToHost, stream_), "read slots");
     }
     ok = ok && check(hipStreamSynchronize(stream_), "delta slots");
-    for (void* p : {static_cast<void*>(d_in), static_cast<void*>(d_slots), static_cast<void*>(d_plans), d_temp})
-        if (p) (void)hipFree(p);
     if (ok)
         for (size_t u = 0; u < plans.size(); ++u) plans[u].slots = slots[u];
     return ok;
@@ -993,18 +981,15 @@ bool GpuTiler::owner_shares(std::vector<UnitPlan>& plans, uint32_t max_span) {
     std::vector<uint64_t> start(nu);
     std::vector<uint32_t> count(nu);
     for (uint32_t u = 0; u < nu; ++u) { start[u] = plans[u].scratch; count[u] = plans[u].n; }
-    uint64_t* d_start = nullptr;
-    uint32_t *d_n = nullptr, *d_own = nullptr;
+    DeviceBuffer<uint64_t> d_start;
+    DeviceBuffer<uint32_t> d_n, d_own;
     std::vector<uint32_t> own(size_t(nu) * kShareWords);
-    bool ok = check(upload(&d_start, start, stream_), "upload") && check(upload(&d_n, count, stream_), "upload") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_own), own.size() * 4), "hipMalloc");
+    bool ok = check(upload(d_start, start, stream_), "upload") && check(upload(d_n, count, stream_), "upload") && check(d_own.alloc_count(own.size()), "hipMalloc");
     if (ok) {
-        hipLaunchKernelGGL(owner_balanced_shares_kernel, dim3((nu + 255) / 256), dim3(256), 0, stream_, d_start, d_n, nu, d_keys_, max_span, d_own);
-        ok = check(hipGetLastError(), "owner_balanced_shares_kernel") && check(hipMemcpyAsync(own.data(), d_own, own.size() * 4, hipMemcpyDeviceToHost, stream_), "read shares") &&
-             check(hipStreamSynchronize(stream_), "owner shares");
+        hipLaunchKernelGGL(owner_balanced_shares_kernel, dim3((nu + 255) / 256), dim3(256), 0, stream_, d_start.get(), d_n.get(), nu, d_keys_.get(), max_span, d_own.get());
+        ok = check(hipGetLastError(), "owner_balanced_shares_kernel") &&
+             check(hipMemcpyAsync(own.data(), d_own.get(), own.size() * 4, hipMemcpyDeviceToHost, stream_), "read shares") && check(hipStreamSynchronize(stream_), "owner shares");
     }
-    for (void* p : {static_cast<void*>(d_start), static_cast<void*>(d_n), static_cast<void*>(d_own)})
-        if (p) (void)hipFree(p);
     if (ok)
         for (uint32_t u = 0; u < nu; ++u) {
             const uint32_t* o = own.data() + size_t(u) * kShareWords;
@@ -1021,63 +1006,61 @@ bool GpuTiler::emit(StreamFormat format, uint64_t image_bytes, uint64_t slack_by
                     const std::vector<uint32_t>& block_of_unit, const std::vector<Block>& blocks, bool is_float) {
     std::vector<DevicePlan> dp;
     make_device_plans(plans, block_of_unit, blocks, dp);
-    DevicePlan* d_plans = nullptr;
+    DeviceBuffer<DevicePlan> d_plans;
     const size_t bytes = std::max<uint64_t>(image_bytes + slack_bytes, 256);
-    bool ok = check(hipMalloc(reinterpret_cast<void**>(&d_image_), bytes), "hipMalloc(image)") && check(hipMemsetAsync(d_image_, 0, bytes, stream_), "hipMemset(image)") &&
-              check(upload(&d_plans, dp, stream_), "upload plans");
-    if (ok && d_src_) ok = alloc_map(&d_map_, image_bytes);
+    bool ok = check(d_image_.alloc(bytes), "hipMalloc(image)") && check(hipMemsetAsync(d_image_.get(), 0, bytes, stream_), "hipMemset(image)") &&
+              check(upload(d_plans, dp, stream_), "upload plans");
+    if (ok && d_src_) ok = alloc_map(d_map_, image_bytes);
     const dim3 grid(uint32_t(plans.size())), block(256);
     if (ok && !plans.empty()) {
-        const bool m = d_map_ != nullptr;
+        const bool m = bool(d_map_);
+        const DevicePlan* p = d_plans.get();
+        const uint64_t* keys = d_keys_.get();
+        const uint32_t *vals = d_vals_.get(), *src = d_src_.get();
+        uint8_t* image = d_image_.get();
+        uint32_t* map = d_map_.get();
         switch (format) {
             case kFormatPairs:
-                hipLaunchKernelGGL((m ? emit_pairs_kernel<false, true> : emit_pairs_kernel<false, false>), grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_, d_src_, d_map_);
+                hipLaunchKernelGGL((m ? emit_pairs_kernel<false, true> : emit_pairs_kernel<false, false>), grid, block, 0, stream_, p, keys, vals, image, src, map);
                 break;
             case kFormatPairs24:
-                hipLaunchKernelGGL((m ? emit_pairs_kernel<true, true> : emit_pairs_kernel<true, false>), grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_, d_src_, d_map_);
+                hipLaunchKernelGGL((m ? emit_pairs_kernel<true, true> : emit_pairs_kernel<true, false>), grid, block, 0, stream_, p, keys, vals, image, src, map);
                 break;
             case kFormatOwner:
-                hipLaunchKernelGGL((m ? emit_owner_kernel<false, true> : emit_owner_kernel<false, false>), grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_, d_src_, d_map_);
+                hipLaunchKernelGGL((m ? emit_owner_kernel<false, true> : emit_owner_kernel<false, false>), grid, block, 0, stream_, p, keys, vals, image, src, map);
                 break;
             case kFormatOwner24:
-                hipLaunchKernelGGL((m ? emit_owner_kernel<true, true> : emit_owner_kernel<true, false>), grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_image_, d_src_, d_map_);
+                hipLaunchKernelGGL((m ? emit_owner_kernel<true, true> : emit_owner_kernel<true, false>), grid, block, 0, stream_, p, keys, vals, image, src, map);
                 break;
             case kFormatDelta:
-                hipLaunchKernelGGL(m ? emit_delta_kernel<true> : emit_delta_kernel<false>, grid, block, 0, stream_, d_plans, d_keys_, d_vals_, d_bridges_, d_image_,
-                                   is_float ? kBridgeGap : 0u, d_src_, d_map_);
+                hipLaunchKernelGGL(m ? emit_delta_kernel<true> : emit_delta_kernel<false>, grid, block, 0, stream_, p, keys, vals, d_bridges_.get(), image,
+                                   is_float ? kBridgeGap : 0u, src, map);
                 break;
             default: ok = fail("gpu re-tile: format not supported");
         }
         ok = ok && check(hipGetLastError(), "emit kernel");
     }
     ok = ok && check(hipStreamSynchronize(stream_), "emit");
-    if (d_plans) (void)hipFree(d_plans);
-    for (void** p : {reinterpret_cast<void**>(&d_keys_), reinterpret_cast<void**>(&d_vals_), reinterpret_cast<void**>(&d_bridges_), reinterpret_cast<void**>(&d_src_)})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    // keys, values, bridges and sources go back now; a failed emit keeps image and map until the tiler goes (bitmap_emit and sweep_emit give theirs back at once)
+    d_keys_.reset();
+    d_vals_.reset();
+    d_bridges_.reset();
+    d_src_.reset();
     return ok;
 }
 
 // ---- BITMAP ------------------------------------------------------------------------------------------------------------------------
 bool GpuTiler::bitmap_slice_counts(uint32_t slices, uint32_t GR, std::vector<uint32_t>& cnt) {
     cnt.assign(size_t(L_.num_rows) * slices, 0);
-    ElementSource src{d_channels_, static_cast<const StreamGroup*>(d_groups_), d_advance_, d_indptr_, d_indices_, d_values_, total_, num_groups_, total_slots_,
-                      L_.num_rows, csr_ ? csr_->num_cols : L_.num_cols, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), csr_ ? 1u : 0u};
-    const uint64_t threads = csr_ ? (total_ + kCsrSegment - 1) / kCsrSegment : total_slots_;
-    uint32_t* d_cnt = nullptr;
-    bool ok = check(hipMalloc(reinterpret_cast<void**>(&d_cnt), std::max<size_t>(cnt.size() * 4, 16)), "hipMalloc") &&
-              check(hipMemsetAsync(d_cnt, 0, cnt.size() * 4, stream_), "hipMemset");
+    const uint64_t threads = element_threads();
+    DeviceBuffer<uint32_t> d_cnt;
+    bool ok = check(d_cnt.alloc_count(cnt.size(), 16), "hipMalloc") && check(hipMemsetAsync(d_cnt.get(), 0, cnt.size() * 4, stream_), "hipMemset");
     if (ok && threads) {
-        hipLaunchKernelGGL(bitmap_slice_counts_kernel, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, src, slices, GR, d_cnt, d_scalar_);
+        hipLaunchKernelGGL(bitmap_slice_counts_kernel, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, source<ElementSource>(), slices, GR, d_cnt.get(), d_scalar_.get());
         ok = check(hipGetLastError(), "bitmap_slice_counts_kernel");
     }
-    ok = ok && (cnt.empty() || check(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * 4, hipMemcpyDeviceToHost, stream_), "read slice counts"));
-    if (ok) {
-        uint32_t words[3] = {0, 0, 0};
-        ok = check(hipMemcpyAsync(words, d_scalar_, 12, hipMemcpyDeviceToHost, stream_), "slice counts") && check(hipStreamSynchronize(stream_), "slice counts");
-        if (ok && words[0]) ok = fail("CSR row " + std::to_string(uint64_t(words[1]) * PACK_SIZE + words[2]) + ": column index outside the matrix");
-    }
-    if (d_cnt) (void)hipFree(d_cnt);
-    return ok;
+    return ok && (cnt.empty() || check(hipMemcpyAsync(cnt.data(), d_cnt.get(), cnt.size() * 4, hipMemcpyDeviceToHost, stream_), "read slice counts")) &&
+           read_error("slice counts", "slice counts");
 }
 
 bool GpuTiler::bitmap_emit(uint32_t slices, uint32_t GR, const std::vector<uint32_t>& range_of_row, const std::vector<BitmapBlock>& blocks,
@@ -1085,9 +1068,8 @@ bool GpuTiler::bitmap_emit(uint32_t slices, uint32_t GR, const std::vector<uint3
                            std::vector<uint32_t>& run_prefix, std::vector<uint64_t>& run_heads, const MfmaImage* mfma, bool& duplicates) {
     detail::PhaseTimer timer;
     duplicates = false;
-    ElementSource src{d_channels_, static_cast<const StreamGroup*>(d_groups_), d_advance_, d_indptr_, d_indices_, d_values_, total_, num_groups_, total_slots_,
-                      L_.num_rows, csr_ ? csr_->num_cols : L_.num_cols, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), csr_ ? 1u : 0u};
-    const uint64_t threads = csr_ ? (total_ + kCsrSegment - 1) / kCsrSegment : total_slots_;
+    const ElementSource src = source<ElementSource>();
+    const uint64_t threads = element_threads();
     const dim3 egrid(uint32_t((threads + 255) / 256)), block(256);
     uint64_t prefix_words = 0;
     for (const BitmapBlock& b : blocks) prefix_words = std::max<uint64_t>(prefix_words, b.prefix0 + uint64_t(b.nrows) * b.stride);
@@ -1095,91 +1077,87 @@ bool GpuTiler::bitmap_emit(uint32_t slices, uint32_t GR, const std::vector<uint3
     const uint32_t num_runs = uint32_t(runs.size());
     run_prefix.assign(num_runs, 0);
     run_heads.assign(size_t(num_runs) * kBitmapMaskBatch, 0);
-    uint32_t *d_range = nullptr, *d_prefix = nullptr, *d_flags = nullptr, *d_run_prefix = nullptr, *d_cnt = nullptr, *d_pos = nullptr;
-    BitmapBlock* d_blocks = nullptr;
-    BitmapRun* d_runs = nullptr;
-    uint64_t* d_row_base = nullptr;
-    unsigned long long* d_heads = nullptr;
-    void* d_temp = nullptr;
-    bool ok = check(hipMalloc(reinterpret_cast<void**>(&d_image_), bytes), "hipMalloc(image)") && check(hipMemsetAsync(d_image_, 0, bytes, stream_), "hipMemset(image)") &&
-              check(upload(&d_range, range_of_row, stream_), "upload row ranges") && check(upload(&d_blocks, blocks, stream_), "upload blocks") &&
-              check(upload(&d_row_base, row_value_base, stream_), "upload row bases") && check(upload(&d_runs, runs, stream_), "upload runs") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_prefix), std::max<size_t>(prefix_words * 4, 16)), "hipMalloc(prefix)") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_flags), 16), "hipMalloc") && check(hipMemsetAsync(d_flags, 0, 16, stream_), "hipMemset") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_run_prefix), std::max<size_t>(size_t(num_runs) * 4, 16)), "hipMalloc") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_heads), std::max<size_t>(run_heads.size() * 8, 16)), "hipMalloc");
-    unsigned long long* image64 = reinterpret_cast<unsigned long long*>(d_image_);
+    DeviceBuffer<uint32_t> d_range, d_prefix, d_flags, d_run_prefix, d_cnt, d_pos;
+    DeviceBuffer<BitmapBlock> d_blocks;
+    DeviceBuffer<BitmapRun> d_runs;
+    DeviceBuffer<uint64_t> d_row_base;
+    DeviceBuffer<unsigned long long> d_heads;
+    DeviceBuffer<uint8_t> d_temp;
+    bool ok = check(d_image_.alloc(bytes), "hipMalloc(image)") && check(hipMemsetAsync(d_image_.get(), 0, bytes, stream_), "hipMemset(image)") &&
+              check(upload(d_range, range_of_row, stream_), "upload row ranges") && check(upload(d_blocks, blocks, stream_), "upload blocks") &&
+              check(upload(d_row_base, row_value_base, stream_), "upload row bases") && check(upload(d_runs, runs, stream_), "upload runs") &&
+              check(d_prefix.alloc_count(prefix_words, 16), "hipMalloc(prefix)") &&
+              check(d_flags.alloc(16), "hipMalloc") && check(hipMemsetAsync(d_flags.get(), 0, 16, stream_), "hipMemset") &&
+              check(d_run_prefix.alloc_count(num_runs, 16), "hipMalloc") && check(d_heads.alloc_count(run_heads.size(), 16), "hipMalloc");
+    unsigned long long* image64 = reinterpret_cast<unsigned long long*>(d_image_.get());
     unsigned long long* masks2 = nullptr;
     if (ok && mfma) {
-        ok = check(hipMalloc(reinterpret_cast<void**>(&d_mfma_), std::max<size_t>(mfma->words_bytes, 16)), "hipMalloc(second image)") &&
-             check(hipMemsetAsync(d_mfma_, 0, mfma->words_bytes, stream_), "hipMemset(second image)");
-        masks2 = reinterpret_cast<unsigned long long*>(d_mfma_);
+        ok = check(d_mfma_.alloc_count(mfma->words_bytes, 16), "hipMalloc(second image)") &&
+             check(hipMemsetAsync(d_mfma_.get(), 0, mfma->words_bytes, stream_), "hipMemset(second image)");
+        masks2 = reinterpret_cast<unsigned long long*>(d_mfma_.get());
     }
     if (ok && threads) {
-        hipLaunchKernelGGL(bitmap_masks_kernel, egrid, block, 0, stream_, src, slices, GR, d_range, d_blocks, image64, masks2, d_flags, d_scalar_);
+        hipLaunchKernelGGL(bitmap_masks_kernel, egrid, block, 0, stream_, src, slices, GR, d_range.get(), d_blocks.get(), image64, masks2, d_flags.get(), d_scalar_.get());
         ok = check(hipGetLastError(), "bitmap_masks_kernel");
     }
-    uint32_t flags[4] = {0, 0, 0, 0}, errw[3] = {0, 0, 0};
-    ok = ok && check(hipMemcpyAsync(flags, d_flags, 16, hipMemcpyDeviceToHost, stream_), "read flags") &&
-         check(hipMemcpyAsync(errw, d_scalar_, 12, hipMemcpyDeviceToHost, stream_), "read flags") && check(hipStreamSynchronize(stream_), "bitmap masks");
-    if (ok && errw[0]) ok = fail("CSR row " + std::to_string(uint64_t(errw[1]) * PACK_SIZE + errw[2]) + ": column index outside the matrix");
+    uint32_t flags[4] = {0, 0, 0, 0};
+    ok = ok && check(hipMemcpyAsync(flags, d_flags.get(), 16, hipMemcpyDeviceToHost, stream_), "read flags") && read_error("read flags", "bitmap masks");
     timer.lap("gpu: bitmap masks");
     duplicates = ok && flags[0] != 0;
     // value map: one for the image and one for the second image, or none (either too large for 32-bit word indices)
     if (ok && !duplicates && value_map_ && image_bytes / 4 < kMapMaxWords && !(mfma && mfma->words_bytes / 4 >= kMapMaxWords)) {
-        ok = alloc_map(&d_map_, image_bytes) && (!mfma || alloc_map(&d_map2_, mfma->words_bytes));
+        ok = alloc_map(d_map_, image_bytes) && (!mfma || alloc_map(d_map2_, mfma->words_bytes));
     }
     if (ok && !duplicates) {
         const uint64_t waves = uint64_t(L_.num_rows) * slices;
         if (waves) {
-            hipLaunchKernelGGL(bitmap_prefix_kernel, dim3(uint32_t((waves * kWaveLanes + 255) / 256)), block, 0, stream_, L_.num_rows, slices, d_range, d_blocks, image64, d_prefix);
+            hipLaunchKernelGGL(bitmap_prefix_kernel, dim3(uint32_t((waves * kWaveLanes + 255) / 256)), block, 0, stream_, L_.num_rows, slices, d_range.get(), d_blocks.get(), image64,
+                               d_prefix.get());
             ok = check(hipGetLastError(), "bitmap_prefix_kernel");
         }
         if (ok && threads) {
-            hipLaunchKernelGGL(d_map_ ? bitmap_values_kernel<true> : bitmap_values_kernel<false>, egrid, block, 0, stream_, src, slices, GR, d_range, d_blocks,
-                               d_row_base, d_prefix, d_image_, d_scalar_, d_map_);
+            hipLaunchKernelGGL(d_map_ ? bitmap_values_kernel<true> : bitmap_values_kernel<false>, egrid, block, 0, stream_, src, slices, GR, d_range.get(), d_blocks.get(),
+                               d_row_base.get(), d_prefix.get(), d_image_.get(), d_scalar_.get(), d_map_.get());
             ok = check(hipGetLastError(), "bitmap_values_kernel");
         }
         if (ok && num_runs) {
-            hipLaunchKernelGGL(bitmap_run_heads_kernel, dim3((num_runs * kBitmapMaskBatch + 255) / 256), block, 0, stream_, d_runs, num_runs, image64, d_prefix, d_run_prefix, d_heads);
+            hipLaunchKernelGGL(bitmap_run_heads_kernel, dim3((num_runs * kBitmapMaskBatch + 255) / 256), block, 0, stream_, d_runs.get(), num_runs, image64, d_prefix.get(),
+                               d_run_prefix.get(), d_heads.get());
             ok = check(hipGetLastError(), "bitmap_run_heads_kernel") &&
-                 check(hipMemcpyAsync(run_prefix.data(), d_run_prefix, size_t(num_runs) * 4, hipMemcpyDeviceToHost, stream_), "read run offsets") &&
-                 check(hipMemcpyAsync(run_heads.data(), d_heads, run_heads.size() * 8, hipMemcpyDeviceToHost, stream_), "read run heads");
+                 check(hipMemcpyAsync(run_prefix.data(), d_run_prefix.get(), size_t(num_runs) * 4, hipMemcpyDeviceToHost, stream_), "read run offsets") &&
+                 check(hipMemcpyAsync(run_heads.data(), d_heads.get(), run_heads.size() * 8, hipMemcpyDeviceToHost, stream_), "read run heads");
         }
         if (ok && mfma) {       // [masks: tiles x groups x 16 x 8 bytes][first value of every unit][values]
             const uint64_t tile_groups = uint64_t(mfma->tiles) * mfma->groups;
-            uint32_t* words = reinterpret_cast<uint32_t*>(d_mfma_);
+            uint32_t* words = reinterpret_cast<uint32_t*>(d_mfma_.get());
             size_t temp_bytes = 0;
-            ok = check(hipMalloc(reinterpret_cast<void**>(&d_cnt), (tile_groups + 1) * 4), "hipMalloc") && check(hipMalloc(reinterpret_cast<void**>(&d_pos), (tile_groups + 1) * 4), "hipMalloc") &&
-                 check(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_cnt, d_pos, tile_groups + 1, stream_), "scan (size)") &&
-                 check(hipMalloc(&d_temp, std::max<size_t>(temp_bytes, 16)), "hipMalloc(scan)");
+            ok = check(d_cnt.alloc_count(tile_groups + 1), "hipMalloc") && check(d_pos.alloc_count(tile_groups + 1), "hipMalloc") &&
+                 check(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_cnt.get(), d_pos.get(), tile_groups + 1, stream_), "scan (size)") &&
+                 check(d_temp.alloc_count(temp_bytes, 16), "hipMalloc(scan)");
             if (ok) {
-                hipLaunchKernelGGL(mfma_group_counts_kernel, dim3(uint32_t((tile_groups + 1 + 255) / 256)), block, 0, stream_, masks2, tile_groups, d_cnt);
+                hipLaunchKernelGGL(mfma_group_counts_kernel, dim3(uint32_t((tile_groups + 1 + 255) / 256)), block, 0, stream_, masks2, tile_groups, d_cnt.get());
                 ok = check(hipGetLastError(), "mfma_group_counts_kernel") &&
-                     check(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_cnt, d_pos, tile_groups + 1, stream_), "scan");
+                     check(hipcub::DeviceScan::ExclusiveSum(d_temp.get(), temp_bytes, d_cnt.get(), d_pos.get(), tile_groups + 1, stream_), "scan");
             }
             if (ok) {
-                hipLaunchKernelGGL(mfma_unit_base_kernel, dim3((mfma->tiles * mfma->chunks + 255) / 256), block, 0, stream_, d_pos, mfma->tiles, mfma->groups, mfma->chunk,
+                hipLaunchKernelGGL(mfma_unit_base_kernel, dim3((mfma->tiles * mfma->chunks + 255) / 256), block, 0, stream_, d_pos.get(), mfma->tiles, mfma->groups, mfma->chunk,
                                    mfma->chunks, words + mfma->offsets_word);
                 ok = check(hipGetLastError(), "mfma_unit_base_kernel");
             }
             if (ok && threads) {
-                hipLaunchKernelGGL(d_map2_ ? mfma_values_kernel<true> : mfma_values_kernel<false>, egrid, block, 0, stream_, src, mfma->groups, masks2, d_pos,
-                                   words + mfma->values_word, d_scalar_, uint64_t(mfma->values_word), d_map2_);
+                hipLaunchKernelGGL(d_map2_ ? mfma_values_kernel<true> : mfma_values_kernel<false>, egrid, block, 0, stream_, src, mfma->groups, masks2, d_pos.get(),
+                                   words + mfma->values_word, d_scalar_.get(), uint64_t(mfma->values_word), d_map2_.get());
                 ok = check(hipGetLastError(), "mfma_values_kernel");
             }
         }
     }
     ok = ok && check(hipStreamSynchronize(stream_), "bitmap emit");
     timer.lap("gpu: bitmap prefix + values + run heads + second image");
-    for (void* p : {static_cast<void*>(d_range), static_cast<void*>(d_prefix), static_cast<void*>(d_flags), static_cast<void*>(d_run_prefix), static_cast<void*>(d_cnt),
-                    static_cast<void*>(d_pos), static_cast<void*>(d_blocks), static_cast<void*>(d_runs), static_cast<void*>(d_row_base), static_cast<void*>(d_heads), d_temp})
-        if (p) (void)hipFree(p);
-    if (!ok || duplicates) {
-        if (d_image_) { (void)hipFree(d_image_); d_image_ = nullptr; }
-        if (d_mfma_) { (void)hipFree(d_mfma_); d_mfma_ = nullptr; }
-        if (d_map_) { (void)hipFree(d_map_); d_map_ = nullptr; }
-        if (d_map2_) { (void)hipFree(d_map2_); d_map2_ = nullptr; }
+    if (!ok || duplicates) {      // nothing of a failed emit (or one the host builder repeats) stays; emit keeps its image until the tiler goes
+        d_image_.reset();
+        d_mfma_.reset();
+        d_map_.reset();
+        d_map2_.reset();
     }
     return ok;
 }
@@ -1258,22 +1236,17 @@ __global__ __launch_bounds__(256) void sweep_emit_kernel(const GpuTiler::SweepBl
 }  // namespace
 
 bool GpuTiler::sweep_line_counts(uint32_t lines, std::vector<uint64_t>& line_nnz) {
-    ElementSource src{d_channels_, static_cast<const StreamGroup*>(d_groups_), d_advance_, d_indptr_, d_indices_, d_values_, total_, num_groups_, total_slots_,
-                      L_.num_rows, csr_ ? csr_->num_cols : L_.num_cols, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), csr_ ? 1u : 0u};
-    const uint64_t threads = csr_ ? (total_ + kCsrSegment - 1) / kCsrSegment : total_slots_;
-    uint32_t* d_cnt = nullptr;
+    const uint64_t threads = element_threads();
+    DeviceBuffer<uint32_t> d_cnt;
     std::vector<uint32_t> cnt(lines, 0);
-    bool ok = check(hipMalloc(reinterpret_cast<void**>(&d_cnt), std::max<size_t>(size_t(lines) * 4, 16)), "hipMalloc(line counts)") &&
-              check(hipMemsetAsync(d_cnt, 0, std::max<size_t>(size_t(lines) * 4, 16), stream_), "hipMemset");
+    bool ok = check(d_cnt.alloc_count(lines, 16), "hipMalloc(line counts)") &&
+              check(hipMemsetAsync(d_cnt.get(), 0, std::max<size_t>(size_t(lines) * 4, 16), stream_), "hipMemset");
     if (ok && threads) {
-        hipLaunchKernelGGL(sweep_lines_kernel, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, src, d_cnt, d_scalar_);
+        hipLaunchKernelGGL(sweep_lines_kernel, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, source<ElementSource>(), d_cnt.get(), d_scalar_.get());
         ok = check(hipGetLastError(), "sweep_lines_kernel");
     }
-    uint32_t errw[3] = {0, 0, 0};
-    ok = ok && check(hipMemcpyAsync(cnt.data(), d_cnt, size_t(lines) * 4, hipMemcpyDeviceToHost, stream_), "read line counts") &&
-         check(hipMemcpyAsync(errw, d_scalar_, 12, hipMemcpyDeviceToHost, stream_), "read flags") && check(hipStreamSynchronize(stream_), "sweep line counts");
-    if (ok && errw[0]) ok = fail("CSR row " + std::to_string(uint64_t(errw[1]) * PACK_SIZE + errw[2]) + ": column index outside the matrix");
-    if (d_cnt) (void)hipFree(d_cnt);
+    ok = ok && check(hipMemcpyAsync(cnt.data(), d_cnt.get(), size_t(lines) * 4, hipMemcpyDeviceToHost, stream_), "read line counts") &&
+         read_error("read flags", "sweep line counts");
     line_nnz.assign(cnt.begin(), cnt.end());
     return ok;
 }
@@ -1282,27 +1255,25 @@ bool GpuTiler::sweep_sort(const std::vector<uint32_t>& range_of_row, const std::
                           uint32_t num_blocks, std::vector<uint64_t>& block_start, bool& unsupported) {
     detail::PhaseTimer timer;
     unsupported = false;
-    ElementSource src{d_channels_, static_cast<const StreamGroup*>(d_groups_), d_advance_, d_indptr_, d_indices_, d_values_, total_, num_groups_, total_slots_,
-                      L_.num_rows, csr_ ? csr_->num_cols : L_.num_cols, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), csr_ ? 1u : 0u};
-    const uint64_t threads = csr_ ? (total_ + kCsrSegment - 1) / kCsrSegment : total_slots_;
+    const uint64_t threads = element_threads();
     SweepSlices sl{};
     sl.n = uint32_t(slice_col.size()) - 1;
     for (uint32_t k = 0; k <= sl.n; ++k) sl.col[k] = slice_col[k];
     const size_t n = std::max<uint64_t>(total_, 1);
-    uint32_t *d_range = nullptr, *d_row0 = nullptr, *d_vals_in = nullptr, *d_flags = nullptr;
-    uint64_t* d_keys_in = nullptr;
-    unsigned long long *d_cursor = nullptr, *d_start = nullptr;
-    void* d_temp = nullptr;
-    bool ok = check(upload(&d_range, range_of_row, stream_), "upload row ranges") && check(upload(&d_row0, range_row0, stream_), "upload range rows") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_keys_in), n * 8), "hipMalloc(keys)") && check(hipMalloc(reinterpret_cast<void**>(&d_vals_in), n * 4), "hipMalloc(values)") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_keys_), n * 8), "hipMalloc(keys)") && check(hipMalloc(reinterpret_cast<void**>(&d_vals_), n * 4), "hipMalloc(values)") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_cursor), 8), "hipMalloc") && check(hipMemsetAsync(d_cursor, 0, 8, stream_), "hipMemset") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_flags), 16), "hipMalloc") && check(hipMemsetAsync(d_flags, 0, 16, stream_), "hipMemset") &&
-              check(hipMalloc(reinterpret_cast<void**>(&d_start), (size_t(num_blocks) + 1) * 8), "hipMalloc(block starts)") &&
-              check(hipMemsetAsync(d_start, 0xff, (size_t(num_blocks) + 1) * 8, stream_), "hipMemset");
+    DeviceBuffer<uint32_t> d_range, d_row0, d_vals_in, d_flags;
+    DeviceBuffer<uint64_t> d_keys_in;
+    DeviceBuffer<unsigned long long> d_cursor, d_start;
+    DeviceBuffer<uint8_t> d_temp;
+    bool ok = check(upload(d_range, range_of_row, stream_), "upload row ranges") && check(upload(d_row0, range_row0, stream_), "upload range rows") &&
+              check(d_keys_in.alloc_count(n), "hipMalloc(keys)") && check(d_vals_in.alloc_count(n), "hipMalloc(values)") &&
+              check(d_keys_.alloc_count(n), "hipMalloc(keys)") && check(d_vals_.alloc_count(n), "hipMalloc(values)") &&
+              check(d_cursor.alloc(8), "hipMalloc") && check(hipMemsetAsync(d_cursor.get(), 0, 8, stream_), "hipMemset") &&
+              check(d_flags.alloc(16), "hipMalloc") && check(hipMemsetAsync(d_flags.get(), 0, 16, stream_), "hipMemset") &&
+              check(d_start.alloc_count(size_t(num_blocks) + 1), "hipMalloc(block starts)") &&
+              check(hipMemsetAsync(d_start.get(), 0xff, (size_t(num_blocks) + 1) * 8, stream_), "hipMemset");
     if (ok && threads) {
-        hipLaunchKernelGGL(value_map_ ? sweep_keys_kernel<true> : sweep_keys_kernel<false>, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_, src, d_range,
-                           d_row0, sl, d_cursor, d_keys_in, d_vals_in, d_scalar_);
+        hipLaunchKernelGGL(value_map_ ? sweep_keys_kernel<true> : sweep_keys_kernel<false>, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, stream_,
+                           source<ElementSource>(), d_range.get(), d_row0.get(), sl, d_cursor.get(), d_keys_in.get(), d_vals_in.get(), d_scalar_.get());
         ok = check(hipGetLastError(), "sweep_keys_kernel");
     }
     if (timer.on) { (void)hipStreamSynchronize(stream_); timer.lap("gpu: sweep keys"); }
@@ -1311,34 +1282,29 @@ bool GpuTiler::sweep_sort(const std::vector<uint32_t>& range_of_row, const std::
         while ((uint64_t(1) << block_bits) < num_blocks) ++block_bits;
         size_t temp_bytes = 0;
         const int end_bit = int(48 + block_bits);
-        ok = end_bit <= 64 && check(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys_in, d_keys_, d_vals_in, d_vals_, total_, 0, end_bit, stream_), "radix sort (size)") &&
-             check(hipMalloc(&d_temp, std::max<size_t>(temp_bytes, 16)), "hipMalloc(sort)") &&
-             check(hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, d_keys_in, d_keys_, d_vals_in, d_vals_, total_, 0, end_bit, stream_), "radix sort");
+        ok = end_bit <= 64 && check(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys_in.get(), d_keys_.get(), d_vals_in.get(), d_vals_.get(), total_, 0, end_bit, stream_), "radix sort (size)") &&
+             check(d_temp.alloc_count(temp_bytes, 16), "hipMalloc(sort)") &&
+             check(hipcub::DeviceRadixSort::SortPairs(d_temp.get(), temp_bytes, d_keys_in.get(), d_keys_.get(), d_vals_in.get(), d_vals_.get(), total_, 0, end_bit, stream_), "radix sort");
         if (ok && value_map_) ok = gather_values();
         if (ok) {
             const dim3 grid(uint32_t((total_ + 255) / 256));
-            hipLaunchKernelGGL(sweep_starts_kernel, grid, dim3(256), 0, stream_, d_keys_, total_, d_start, d_flags);
-            hipLaunchKernelGGL(sweep_spans_kernel, grid, dim3(256), 0, stream_, d_keys_, total_, d_start, d_flags);
+            hipLaunchKernelGGL(sweep_starts_kernel, grid, dim3(256), 0, stream_, d_keys_.get(), total_, d_start.get(), d_flags.get());
+            hipLaunchKernelGGL(sweep_spans_kernel, grid, dim3(256), 0, stream_, d_keys_.get(), total_, d_start.get(), d_flags.get());
             ok = check(hipGetLastError(), "sweep_starts_kernel");
         }
     }
     std::vector<unsigned long long> starts(size_t(num_blocks) + 1, ~0ull);
     uint32_t flags[4] = {0, 0, 0, 0};
     unsigned long long placed = 0;
-    ok = ok && check(hipMemcpyAsync(starts.data(), d_start, starts.size() * 8, hipMemcpyDeviceToHost, stream_), "read block starts") &&
-         check(hipMemcpyAsync(flags, d_flags, 16, hipMemcpyDeviceToHost, stream_), "read flags") &&
-         check(hipMemcpyAsync(&placed, d_cursor, 8, hipMemcpyDeviceToHost, stream_), "read cursor") && check(hipStreamSynchronize(stream_), "sweep sort");
+    ok = ok && check(hipMemcpyAsync(starts.data(), d_start.get(), starts.size() * 8, hipMemcpyDeviceToHost, stream_), "read block starts") &&
+         check(hipMemcpyAsync(flags, d_flags.get(), 16, hipMemcpyDeviceToHost, stream_), "read flags") &&
+         check(hipMemcpyAsync(&placed, d_cursor.get(), 8, hipMemcpyDeviceToHost, stream_), "read cursor") && check(hipStreamSynchronize(stream_), "sweep sort");
     if (ok && placed != total_) ok = fail("gpu sweep: element count changed between passes");
     timer.lap("gpu: sweep radix sort");
     unsupported = ok && (flags[0] != 0 || flags[1] != 0);
     block_start.assign(size_t(num_blocks) + 1, total_);
     for (uint32_t b = num_blocks; b-- > 0;) block_start[b] = starts[b] == ~0ull ? block_start[b + 1] : starts[b];      // blocks without elements start where the next one does
-    for (void* p : {static_cast<void*>(d_range), static_cast<void*>(d_row0), static_cast<void*>(d_keys_in), static_cast<void*>(d_vals_in), static_cast<void*>(d_flags),
-                    static_cast<void*>(d_cursor), static_cast<void*>(d_start), d_temp})
-        if (p) (void)hipFree(p);
-    if (d_channels_) { (void)hipFree(d_channels_); d_channels_ = nullptr; }      // the source is not needed any more
-    for (void** p : {reinterpret_cast<void**>(&d_indptr_), reinterpret_cast<void**>(&d_indices_), reinterpret_cast<void**>(&d_values_)})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    release_source();
     return ok;
 }
 
@@ -1346,21 +1312,22 @@ bool GpuTiler::sweep_emit(const std::vector<SweepBlock>& blocks, uint64_t image_
     detail::PhaseTimer timer;
     const size_t bytes = std::max<uint64_t>(image_bytes + slack_bytes, 256);
     const uint64_t total_chunks = blocks.empty() ? 0 : blocks.back().chunk0 + uint64_t(blocks.back().steps) * kSweepWaves;
-    SweepBlock* d_blocks = nullptr;
-    bool ok = check(hipMalloc(reinterpret_cast<void**>(&d_image_), bytes), "hipMalloc(image)") && check(upload(&d_blocks, blocks, stream_), "upload blocks");
-    if (ok && slack_bytes) ok = check(hipMemsetAsync(d_image_ + image_bytes, 0, slack_bytes, stream_), "hipMemset(slack)");
-    if (ok && d_src_) ok = alloc_map(&d_map_, image_bytes);
+    DeviceBuffer<SweepBlock> d_blocks;
+    bool ok = check(d_image_.alloc(bytes), "hipMalloc(image)") && check(upload(d_blocks, blocks, stream_), "upload blocks");
+    if (ok && slack_bytes) ok = check(hipMemsetAsync(d_image_.get() + image_bytes, 0, slack_bytes, stream_), "hipMemset(slack)");
+    if (ok && d_src_) ok = alloc_map(d_map_, image_bytes);
     if (ok && total_chunks) {
         hipLaunchKernelGGL(d_map_ ? sweep_emit_kernel<true> : sweep_emit_kernel<false>, dim3(uint32_t((total_chunks * kWaveLanes + 255) / 256)), dim3(256), 0, stream_,
-                           d_blocks, uint32_t(blocks.size()), total_chunks, d_keys_, d_vals_, d_image_, d_src_, d_map_);
+                           d_blocks.get(), uint32_t(blocks.size()), total_chunks, d_keys_.get(), d_vals_.get(), d_image_.get(), d_src_.get(), d_map_.get());
         ok = check(hipGetLastError(), "sweep_emit_kernel");
     }
     ok = ok && check(hipStreamSynchronize(stream_), "sweep emit");
     timer.lap("gpu: sweep emit");
-    if (d_blocks) (void)hipFree(d_blocks);
-    if (d_src_) { (void)hipFree(d_src_); d_src_ = nullptr; }
-    if (!ok && d_image_) { (void)hipFree(d_image_); d_image_ = nullptr; }
-    if (!ok && d_map_) { (void)hipFree(d_map_); d_map_ = nullptr; }
+    d_src_.reset();      // (keys and values stay until the tiler goes; emit gives them back here)
+    if (!ok) {           // nothing of a failed emit stays; emit keeps its image until the tiler goes
+        d_image_.reset();
+        d_map_.reset();
+    }
     return ok;
 }
 

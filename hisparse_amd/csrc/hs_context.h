@@ -17,45 +17,11 @@
 #include <utility>
 #include <vector>
 
+#include "device_buffer.h"      // DeviceBuffer, PinnedBuffer, DeviceEvent: the owners of device memory, pinned memory, events
 #include "hisparse/common.h"
 #include "spmv_kernels.h"
 #include "stream_tiles.h"
 #include "tiles_common.h"
-
-// Owners of what the HIP runtime hands out: device memory, pinned host memory, events.  Move-only; the destructor gives back.
-template <typename T, hipError_t (*Free)(void*) = hipFree>
-class DeviceBuffer {
-public:
-    DeviceBuffer() = default;
-    ~DeviceBuffer() { reset(); }
-    DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.release()) {}      // (declaring the moves deletes the copies)
-    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept { if (this != &o) adopt(o.release()); return *this; }
-    hipError_t alloc(size_t bytes) { reset(); return hipMalloc(reinterpret_cast<void**>(&p_), bytes); }      // device memory (whatever was held is freed first)
-    void adopt(T* raw) { if (p_) (void)Free(p_); p_ = raw; }
-    T* release() { T* p = p_; p_ = nullptr; return p; }
-    void reset() { adopt(nullptr); }
-    T* get() const { return p_; }
-    explicit operator bool() const { return p_ != nullptr; }
-
-private:
-    T* p_ = nullptr;
-};
-
-template <typename T>
-using PinnedBuffer = DeviceBuffer<T, hipHostFree>;      // hipHostMalloc'ed memory: adopt() the pointer
-
-class DeviceEvent {
-public:
-    DeviceEvent() = default;
-    ~DeviceEvent() { if (e_) (void)hipEventDestroy(e_); }
-    DeviceEvent(DeviceEvent&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
-    DeviceEvent& operator=(DeviceEvent&& o) noexcept { std::swap(e_, o.e_); return *this; }      // (o's destructor gives the old one back)
-    hipError_t create(unsigned flags = hipEventDefault) { return e_ ? hipSuccess : hipEventCreateWithFlags(&e_, flags); }
-    hipEvent_t get() const { return e_; }
-
-private:
-    hipEvent_t e_ = nullptr;
-};
 
 // The host side of the carried combine pass (the device side: spmv_device.h, hisparse::dev::CarriedCombine).
 // Column-sliced plans, hs_run after hs_run on the library's own stream: the combine pass of a step is CARRIED into the SpMV kernel of the

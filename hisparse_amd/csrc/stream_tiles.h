@@ -336,6 +336,7 @@ struct StreamTiles {
     ImageBytes image;                    // element streams, uploaded verbatim (host builder)
     MfmaImage mfma;                      // float BITMAP images only (bitmap_tiles.cpp)
     uint32_t bitmap_x_groups = 0;        // BITMAP: groups of x a block reads (its column slice), when the kernel is to keep that stretch in LDS; else 0
+    // (the four device pointers here and in MfmaImage stay raw: this header is also compiled without the HIP headers (libhisparse_cpu.so) and cannot hold a DeviceBuffer)
     uint8_t* d_image = nullptr;          // GPU builder: the image, already in device memory (image_bytes + slack); the caller owns it
     uint32_t* d_value_map = nullptr;     // GPU builder, CsrView::value_map: per CSR non-zero the u32 word index of its value in d_image; the caller owns it
     uint32_t* d_value_map2 = nullptr;    // ... and in mfma.d_words (float BITMAP matrices with the matrix-engine image)

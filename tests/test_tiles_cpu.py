@@ -465,6 +465,23 @@ def test_worker_pool(tmp_path):
     assert out.returncode == 0 and "WORKER POOL OK" in out.stdout, out.stdout + out.stderr
 
 
+def test_device_buffer(tmp_path):
+    """The owner of device memory (device_buffer.h: DeviceBuffer) frees what it holds exactly once -- destruction, moves, self-move, adopt,
+    release, reset, an exception in the owners' scope: tests/cpp/test_device_buffer.cpp, with a counting Free over host addresses and
+    without the HIP runtime.  alloc / alloc_count are hipMalloc behind reset() and cannot run here: the GPU tests cover them
+    (test_gpu_memory.py)."""
+    import subprocess
+    rocm = "/opt/rocm/include"
+    if not os.path.exists(f"{rocm}/hip/hip_runtime_api.h"):
+        pytest.skip("no HIP headers")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "device_buffer"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", f"-I{rocm}", f"-I{root}/hisparse_amd/csrc",
+                           f"{root}/tests/cpp/test_device_buffer.cpp", "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "DEVICE BUFFER OK" in out.stdout, out.stdout + out.stderr
+
+
 @pytest.mark.parametrize("impl,ob", [(0, 8), (2, 64)])
 def test_blocks_go_to_xcds_by_column_slice(impl, ob, monkeypatch):
     """Column-sliced matrices whose x outgrows an XCD's L2 (forced here: HISPARSE_XCD_AFFINITY=1): logical workgroups
