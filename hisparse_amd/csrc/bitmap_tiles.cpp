@@ -21,7 +21,7 @@ using namespace detail;
 
 bool build_bitmap_tiles(const Layout& L, const void* const channel[NUM_HBM_CHANNELS], const uint64_t n_packets[NUM_HBM_CHANNELS],
                         const std::vector<uint32_t>& row_nnz, uint32_t max_workgroups, StreamTiles& out, std::string& error,
-                        const CsrView* csr, GpuTiler* gpu, uint64_t image_slack) {
+                        const CsrView* csr_in, GpuTiler* gpu, uint64_t image_slack) {
     const uint32_t num_rows = L.num_rows, num_cols = L.num_cols, RP = L.row_parts, CP = L.col_parts;
     const uint32_t G = std::max<uint32_t>(1, max_workgroups);
     // a mask per 64 columns of every row: only sensible for dense rows; when the format is FORCED onto a big sparse matrix
@@ -42,7 +42,9 @@ bool build_bitmap_tiles(const Layout& L, const void* const channel[NUM_HBM_CHANN
     const std::unique_ptr<uint64_t[]> elems_buf(new uint64_t[gpu ? 1 : std::max<uint64_t>(nnz, 1)]);   // (not zeroed: every entry is written below)
     uint64_t* const elems = elems_buf.get();               // column << 32 | value word: sorts by column
     if (gpu) {
-    } else if (csr) {       // the rows are there already; value words as csr_matrix_convert_from_float gives them (sw/data_loader.h:76-84)
+    } else if (csr_in) {    // the rows are there already; value words as csr_matrix_convert_from_float gives them (sw/data_loader.h:76-84)
+        const HostCsr csr(csr_in);      // (a transposed load: A^T's rows, made here)
+        if (!csr.ok()) { error = "CSR column index outside the matrix"; return false; }
         const bool fixed = L.g->impl == IMPL_FIXED;
         std::atomic<bool> bad_column(false);
         parallel_for((csr->num_rows + 1023) / 1024, [&](size_t chunk) {

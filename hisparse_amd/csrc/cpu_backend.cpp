@@ -11,7 +11,7 @@
 //   fixed: every product narrowed to Q8.24 with AP_RND / AP_SAT (spmv/libfpga/pe.h:64), summed in 64 bits, clamped once (pe.h:72;
 //          saturating adds of non-negative terms are order free);
 //   float: one fp32 multiply per product (pe-pob.h:63-65, pe-stall.h:52), summed in double in storage order, rounded to fp32 once.
-// Core entry points only (create / load_matrix / load_matrix_csr / update_values / load_vector / run / run_partition / sync / read_result / stats /
+// Core entry points only (create / load_matrix / load_matrix_csr / load_matrix_csr_transposed / update_values / load_vector / run / run_partition / sync / read_result / stats /
 // time_runs / errors); the device-memory hooks and the extensions answer HS_ERR_UNSUPPORTED.
 #include "hisparse_hip.h"
 
@@ -35,7 +35,8 @@ struct hs_context {
     uint32_t num_rows = 0, num_cols = 0, row_parts = 0, col_parts = 0;
     std::vector<uint64_t> indptr;      // CSR of the padded matrix: absolute columns, value words
     std::vector<uint32_t> indices, words;
-    bool from_csr = false;             // loaded by hs_load_matrix_csr: `words` are in the caller's non-zero order (hs_update_values)
+    bool from_csr = false;             // loaded by hs_load_matrix_csr(_transposed): hs_update_values takes the caller's non-zero order
+    std::vector<uint32_t> value_at;    // hs_load_matrix_csr_transposed: where the caller's non-zero e sits in `words` (empty: at e)
     std::vector<uint32_t> x, y;
     hs_stats stats{};
     std::string error;
@@ -150,6 +151,7 @@ int hs_load_matrix(hs_context* ctx, const void* const channel[HS_NUM_CHANNELS], 
     using namespace hisparse::dev::detail;
     ctx->matrix_loaded = false;
     ctx->from_csr = false;
+    ctx->value_at.clear();
     Layout L;
     L.g = &ctx->geom;
     L.num_rows = num_rows; L.num_cols = num_cols; L.row_parts = num_row_partitions; L.col_parts = num_col_partitions;
@@ -227,6 +229,53 @@ int hs_load_matrix_csr(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, co
         else std::memcpy(&ctx->words[e], &values[e], 4);
     }
     ctx->from_csr = true;
+    ctx->value_at.clear();
+    ctx->stats = hs_stats{};
+    loaded(ctx, uint32_t(rows), uint32_t(cols), uint32_t((rows + g.logical_ob - 1) / g.logical_ob), uint32_t((cols + g.logical_vb - 1) / g.logical_vb), t0);
+    if (padded_rows) *padded_rows = uint32_t(rows);
+    if (padded_cols) *padded_cols = uint32_t(cols);
+    return HS_OK;
+}
+
+// A^T from A's arrays: this library keeps A^T's CSR (the counting sort of csr2csc, hisparse/data_loader.h: rows of A ascending inside a
+// column) and the permutation from the caller's order into it, so that hs_update_values takes A's order here as in the HIP library
+int hs_load_matrix_csr_transposed(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, const float* values,
+                                  uint32_t* padded_rows, uint32_t* padded_cols) {
+    if (!ctx || !indptr) return fail(ctx, HS_ERR_BAD_ARG, "null argument");
+    const Geometry& g = ctx->geom;
+    if (num_rows == 0 || num_cols == 0) return fail(ctx, HS_ERR_BAD_ARG, "empty matrix");
+    const uint64_t rows = (uint64_t(num_cols) + g.row_divisor - 1) / g.row_divisor * g.row_divisor;
+    const uint64_t cols = (uint64_t(num_rows) + hisparse::PACK_SIZE - 1) / hisparse::PACK_SIZE * hisparse::PACK_SIZE;
+    if (rows > 0xffffffffull || cols > 0xffffffffull) return fail(ctx, HS_ERR_BAD_ARG, "padded dimensions exceed 32 bits");
+    if (indptr[0] != 0) return fail(ctx, HS_ERR_BAD_MATRIX, "CSR indptr must start at 0");
+    for (uint32_t r = 0; r < num_rows; ++r)
+        if (indptr[r + 1] < indptr[r]) return fail(ctx, HS_ERR_BAD_MATRIX, "CSR indptr decreases at row " + std::to_string(r));
+    const uint64_t nnz = indptr[num_rows];
+    if (nnz && (!indices || !values)) return fail(ctx, HS_ERR_BAD_ARG, "CSR arrays missing");
+    for (uint64_t e = 0; e < nnz; ++e)
+        if (indices[e] >= num_cols) return fail(ctx, HS_ERR_BAD_MATRIX, "CSR column index outside the matrix");
+    const auto t0 = std::chrono::steady_clock::now();
+    ctx->matrix_loaded = false;
+    spmv::io::CSRMatrix<uint32_t> a;        // the payload is the caller's index of the element
+    a.num_rows = num_rows;
+    a.num_cols = num_cols;
+    a.adj_indptr.assign(indptr, indptr + num_rows + 1);
+    a.adj_indices.assign(indices, indices + nnz);
+    a.adj_data.resize(nnz);
+    for (uint64_t e = 0; e < nnz; ++e) a.adj_data[e] = uint32_t(e);
+    const spmv::io::CSCMatrix<uint32_t> t = spmv::io::csr2csc(a);
+    ctx->indptr.assign(size_t(rows) + 1, nnz);
+    for (uint32_t c = 0; c <= num_cols; ++c) ctx->indptr[c] = t.adj_indptr[c];
+    ctx->indices = t.adj_indices;
+    ctx->words.resize(nnz);
+    ctx->value_at.resize(nnz);
+    for (uint64_t at = 0; at < nnz; ++at) {
+        const uint32_t e = t.adj_data[at];
+        ctx->value_at[e] = uint32_t(at);
+        if (ctx->impl == HS_IMPL_FIXED) ctx->words[at] = hisparse::q8_24_raw_from_double(double(values[e]));     // csr_matrix_convert_from_float
+        else std::memcpy(&ctx->words[at], &values[e], 4);
+    }
+    ctx->from_csr = true;
     ctx->stats = hs_stats{};
     loaded(ctx, uint32_t(rows), uint32_t(cols), uint32_t((rows + g.logical_ob - 1) / g.logical_ob), uint32_t((cols + g.logical_vb - 1) / g.logical_vb), t0);
     if (padded_rows) *padded_rows = uint32_t(rows);
@@ -242,8 +291,9 @@ int hs_update_values(hs_context* ctx, const float* values, uint64_t nnz) {
     if (!ctx->from_csr) return fail(ctx, HS_ERR_UNSUPPORTED, "no value map: the matrix came from hs_load_matrix (CPSR)");
     if (nnz != ctx->words.size()) return fail(ctx, HS_ERR_BAD_ARG, "nnz must equal the loaded CSR's indptr[num_rows] (" + std::to_string(ctx->words.size()) + ")");
     for (uint64_t e = 0; e < nnz; ++e) {
-        if (ctx->impl == HS_IMPL_FIXED) ctx->words[e] = hisparse::q8_24_raw_from_double(double(values[e]));     // csr_matrix_convert_from_float
-        else std::memcpy(&ctx->words[e], &values[e], 4);
+        const uint64_t at = ctx->value_at.empty() ? e : ctx->value_at[e];
+        if (ctx->impl == HS_IMPL_FIXED) ctx->words[at] = hisparse::q8_24_raw_from_double(double(values[e]));     // csr_matrix_convert_from_float
+        else std::memcpy(&ctx->words[at], &values[e], 4);
     }
     return HS_OK;
 }

@@ -37,6 +37,9 @@ class GpuTiler {
     // formats then sort the CSR index as the payload in place of the value word and gather the words after the sort: 4 bytes per
     // non-zero more during the load (`src`, the sorted CSR indices), 4 (+ 4 with a matrix-engine image) kept with the image.
     // Images of 16 GiB or more get no map (the word indices would not fit in 32 bits).
+    // csr.transposed (hs_load_matrix_csr_transposed): the matrix built is A^T of the arrays.  The row counts are a histogram of `indices`
+    // (one more kernel), every element pass takes (row, column) = (indices[e], row of e), and the value-map payload stays e: the image is
+    // byte for byte the one of the host-transposed matrix, the maps are in the order of the arrays passed in.
     GpuTiler(const detail::Layout& layout, const CsrView& csr, hipStream_t stream);
     GpuTiler(const GpuTiler&) = delete;
     GpuTiler& operator=(const GpuTiler&) = delete;
@@ -127,7 +130,8 @@ class GpuTiler {
     std::string error_;
 
     const CsrView* csr_ = nullptr;         // CSR source (then channel_ / n_packets_ are null)
-    DeviceBuffer<uint32_t> d_indptr_;      // CSR source: indptr of the PADDED matrix (num_rows + 1), indices, values
+    uint32_t indptr_rows_ = 0;             // CSR source: rows d_indptr_ covers -- the padded row count, or (transposed) the arrays' num_rows
+    DeviceBuffer<uint32_t> d_indptr_;      // CSR source: indptr of the PADDED matrix (num_rows + 1; transposed: as passed in), indices, values
     DeviceBuffer<uint32_t> d_indices_;
     DeviceBuffer<float> d_values_;
     DeviceBuffer<uint8_t> d_channels_;     // the 16 channel buffers back to back
@@ -145,6 +149,7 @@ class GpuTiler {
     DeviceBuffer<uint8_t> d_image_;
     DeviceBuffer<uint8_t> d_mfma_;         // BITMAP, float modes: the matrix-engine image (stream_tiles.h: MfmaImage)
     bool value_map_ = false;               // CSR source with csr.value_map: build the value maps
+    bool transposed_ = false;              // CSR source, csr.transposed: every pass sees the element (indices[e], row of e) -- the matrix built is A^T
     DeviceBuffer<uint32_t> d_src_;         // value map, element formats: CSR index of every sorted element (beside d_vals_)
     DeviceBuffer<uint32_t> d_map_;         // value map: word index into the image of every non-zero, CSR order
     DeviceBuffer<uint32_t> d_map2_;        // value map: word index into the matrix-engine image

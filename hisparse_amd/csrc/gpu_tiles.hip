@@ -188,6 +188,10 @@ __global__ __launch_bounds__(256) void keys_kernel(const uint8_t* __restrict__ c
 
 // ---- CSR source ---------------------------------------------------------------------------------------------------------------
 // One thread per kCsrSegment consecutive non-zeros: the row of the first one by binary search in indptr, then forward.
+// TRANSPOSED source (CsrView::transposed, hs_load_matrix_csr_transposed): the same arrays, the same cursor, but the element the passes see
+// is (row = indices[e], column = the cursor's row): the element of A^T.  No pass depends on the order the elements arrive in -- a key is
+// the element's whole identity and everything is radix-sorted afterwards -- so the image is the one of the host-transposed matrix.  The
+// value-map payload stays e, the index in the caller's arrays: a map built this way is in A's order.
 constexpr uint32_t kCsrSegment = 16;
 
 struct CsrCursor {
@@ -216,6 +220,33 @@ __device__ __forceinline__ uint32_t word_index(const void* at, const void* base)
 // images whose word indices fit 32 bits (0xffffffff stays the "no entry" fill of a map)
 constexpr uint64_t kMapMaxWords = 0xffffffffull;
 
+// Transposed source: the row counts of A^T are a histogram of A's column indices (a plain source has them in indptr).  row_nnz holds at
+// least num_cols counters; an index outside the matrix is reported with the row of A that holds it (found only then) and counts nowhere.
+__global__ __launch_bounds__(256) void csr_transposed_row_counts_kernel(const uint32_t* __restrict__ indptr, const uint32_t* __restrict__ indices,
+                                                                       uint32_t num_rows, uint64_t nnz, uint32_t num_cols, uint32_t* __restrict__ row_nnz,
+                                                                       uint32_t* scalar) {
+    const uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint64_t begin = t * kCsrSegment, end = min(begin + kCsrSegment, nnz);
+    for (uint64_t e = begin; e < end; ++e) {
+        const uint32_t col = indices[e];
+        if (col >= num_cols) {
+            CsrCursor c;
+            csr_segment(indptr, num_rows, nnz, t, c);
+            while (e >= indptr[c.row + 1]) ++c.row;
+            report(scalar, kErrColumn, c.row / PACK_SIZE, c.row % PACK_SIZE);
+            return;
+        }
+        atomicAdd(row_nnz + col, 1u);
+    }
+}
+
+// The two dedicated CSR kernels (tile counts, sort keys) take the transposed source as a template parameter rather than going through
+// visit_elements: the plain instantiations stay the code they were (the plain load's time does not move), and the key kernel keeps writing
+// element e to slot e without the value conversion a value-map load does not need.  num_rows: the rows indptr covers; num_cols: the bound
+// of `indices` -- both of the ARRAYS.  kT: row = indices[e] (checked against num_cols before it indexes block_of_row), column = c.row.
+// (kT: neighbouring elements fall into different row ranges, so the run below is almost always 1 -- one atomic per non-zero; it is kept
+// because it is correct for any order, not for speed.)
+template <bool kT>
 __global__ __launch_bounds__(256) void csr_count_tiles_kernel(const uint32_t* __restrict__ indptr, const uint32_t* __restrict__ indices, uint32_t num_rows,
                                                              uint64_t nnz, uint32_t num_cols, uint32_t logical_vb, const uint32_t* __restrict__ block_of_row,
                                                              uint32_t tiles, uint32_t S, uint32_t sub_width, uint32_t* __restrict__ cnt, uint32_t* scalar) {
@@ -225,10 +256,11 @@ __global__ __launch_bounds__(256) void csr_count_tiles_kernel(const uint32_t* __
     uint32_t run = 0;
     for (; c.e < c.end; ++c.e) {
         while (c.e >= indptr[c.row + 1]) ++c.row;
-        const uint32_t col = indices[c.e];
-        if (col >= num_cols) { report(scalar, kErrColumn, c.row / PACK_SIZE, c.row % PACK_SIZE); return; }
+        const uint32_t idx = indices[c.e];
+        if (idx >= num_cols) { report(scalar, kErrColumn, c.row / PACK_SIZE, c.row % PACK_SIZE); return; }
+        const uint32_t row = kT ? idx : c.row, col = kT ? c.row : idx;
         const uint32_t cp = col / logical_vb, k = (col - cp * logical_vb) / sub_width;
-        const size_t at = size_t(block_of_row[c.row]) * tiles + cp * S + k;
+        const size_t at = size_t(block_of_row[row]) * tiles + cp * S + k;
         if (at != cur) {
             if (run) atomicAdd(cnt + cur, run);
             cur = at;
@@ -240,7 +272,7 @@ __global__ __launch_bounds__(256) void csr_count_tiles_kernel(const uint32_t* __
 }
 
 // kMap (value map): the sort payload is the CSR index of the element; map_gather_kernel makes the value words after the sort
-template <bool kMap>
+template <bool kMap, bool kT>
 __global__ __launch_bounds__(256) void csr_keys_kernel(const uint32_t* __restrict__ indptr, const uint32_t* __restrict__ indices, const float* __restrict__ values,
                                                       uint32_t num_rows, uint64_t nnz, uint32_t logical_vb, uint32_t fixed,
                                                       const uint32_t* __restrict__ block_of_row, const uint32_t* __restrict__ range_row0,
@@ -250,10 +282,11 @@ __global__ __launch_bounds__(256) void csr_keys_kernel(const uint32_t* __restric
     if (!csr_segment(indptr, num_rows, nnz, uint64_t(blockIdx.x) * blockDim.x + threadIdx.x, c)) return;
     for (; c.e < c.end; ++c.e) {
         while (c.e >= indptr[c.row + 1]) ++c.row;
-        const uint32_t col = indices[c.e], cp = col / logical_vb, local = col - cp * logical_vb, k = local / sub_width;
-        const uint32_t b = block_of_row[c.row];
+        const uint32_t idx = indices[c.e], row = kT ? idx : c.row, col = kT ? c.row : idx;      // (idx: checked by the tile counts)
+        const uint32_t cp = col / logical_vb, local = col - cp * logical_vb, k = local / sub_width;
+        const uint32_t b = block_of_row[row];
         const uint64_t unit = unit_of[size_t(b) * tiles + cp * S + k];
-        const uint64_t pos = uint64_t(c.row - range_row0[b]) * kSubTileCols + (local - k * sub_width);
+        const uint64_t pos = uint64_t(row - range_row0[b]) * kSubTileCols + (local - k * sub_width);
         keys[c.e] = (unit << kPosBits) | pos;
         vals[c.e] = kMap ? uint32_t(c.e) : value_word(values[c.e], fixed != 0);
     }
@@ -481,11 +514,13 @@ struct ElementSource {          // either the uploaded CPSR image or the CSR arr
     const uint32_t* indices;
     const float* values;
     uint64_t nnz;
-    uint32_t num_groups, total_slots, num_rows, num_cols, logical_vb, fixed, csr;
+    uint32_t num_groups, total_slots, num_rows, num_cols, logical_vb, fixed, csr;      // CSR: num_rows / num_cols of the arrays (rows of indptr, bound of indices)
+    uint32_t transposed;    // CSR: the element is (indices[e], the cursor's row)
 };
 
 // visit(row, absolute column, value word) for the elements thread t is responsible for; false + *err on a column outside the matrix.
-// A visit that takes a fourth argument also gets the element's CSR index (the value map; CSR sources only)
+// A visit that takes a fourth argument also gets the element's CSR index (the value map; CSR sources only): the index in the caller's
+// arrays, for a transposed source too
 template <typename Visit>
 __device__ __forceinline__ void visit_elements(const ElementSource& src, uint64_t t, uint32_t* err, Visit visit) {
     if (src.csr) {
@@ -493,10 +528,11 @@ __device__ __forceinline__ void visit_elements(const ElementSource& src, uint64_
         if (!csr_segment(src.indptr, src.num_rows, src.nnz, t, c)) return;
         for (; c.e < c.end; ++c.e) {
             while (c.e >= src.indptr[c.row + 1]) ++c.row;
-            const uint32_t col = src.indices[c.e];
-            if (col >= src.num_cols) { report(err, kErrColumn, c.row / PACK_SIZE, c.row % PACK_SIZE); return; }
-            if constexpr (std::is_invocable_v<Visit, uint32_t, uint32_t, uint32_t, uint64_t>) visit(c.row, col, value_word(src.values[c.e], src.fixed != 0), c.e);
-            else visit(c.row, col, value_word(src.values[c.e], src.fixed != 0));
+            const uint32_t idx = src.indices[c.e];
+            if (idx >= src.num_cols) { report(err, kErrColumn, c.row / PACK_SIZE, c.row % PACK_SIZE); return; }
+            const uint32_t row = src.transposed ? idx : c.row, col = src.transposed ? c.row : idx;
+            if constexpr (std::is_invocable_v<Visit, uint32_t, uint32_t, uint32_t, uint64_t>) visit(row, col, value_word(src.values[c.e], src.fixed != 0), c.e);
+            else visit(row, col, value_word(src.values[c.e], src.fixed != 0));
         }
         return;
     }
@@ -664,7 +700,7 @@ GpuTiler::GpuTiler(const Layout& layout, const void* const channel[NUM_HBM_CHANN
 }
 
 GpuTiler::GpuTiler(const Layout& layout, const CsrView& csr, hipStream_t stream)
-    : L_(layout), geom_(*layout.g), channel_(nullptr), n_packets_(nullptr), stream_(stream), csr_(&csr), value_map_(csr.value_map) {
+    : L_(layout), geom_(*layout.g), channel_(nullptr), n_packets_(nullptr), stream_(stream), csr_(&csr), value_map_(csr.value_map), transposed_(csr.transposed) {
     L_.g = &geom_;
 }
 
@@ -741,7 +777,8 @@ bool GpuTiler::upload_channels() {
 template <typename S>
 S GpuTiler::source() const {
     return S{d_channels_.get(), groups<StreamGroup>(), d_advance_.get(), d_indptr_.get(), d_indices_.get(), d_values_.get(), total_, num_groups_, total_slots_,
-             L_.num_rows, csr_ ? csr_->num_cols : L_.num_cols, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), csr_ ? 1u : 0u};
+             csr_ ? indptr_rows_ : L_.num_rows, csr_ ? csr_->num_cols : L_.num_cols, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED), csr_ ? 1u : 0u,
+             transposed_ ? 1u : 0u};
 }
 uint64_t GpuTiler::element_threads() const { return csr_ ? (total_ + kCsrSegment - 1) / kCsrSegment : total_slots_; }
 
@@ -757,18 +794,24 @@ bool GpuTiler::read_error(const char* copy, const char* sync) {
                 (words[0] == kErrColumn ? "column index outside the column partition" : "decoded row outside the row partition (marker count wrapped?)"));
 }
 
-// CSR source: validate indptr (host, a pass over num_rows words), upload the three arrays; indptr is extended over the padding rows
+// CSR source: validate indptr (host, a pass over num_rows words), upload the three arrays; indptr is extended over the padding rows.
+// Transposed: indptr indexes the COLUMNS of the matrix to build and goes up as it is (num_rows + 1 entries of the arrays, not the row count
+// of A^T); the row counts come from csr_transposed_row_counts_kernel, which also checks every index.
 bool GpuTiler::upload_csr(std::vector<uint32_t>& row_nnz) {
     const CsrView& m = *csr_;
-    if (m.num_rows > L_.num_rows || m.num_cols > L_.num_cols) return fail("CSR matrix larger than the padded dimensions");
+    if (m.out_rows() > L_.num_rows || m.out_cols() > L_.num_cols) return fail("CSR matrix larger than the padded dimensions");
     if (!m.indptr || m.indptr[0] != 0) return fail("CSR indptr must start at 0");
     for (uint32_t r = 0; r < m.num_rows; ++r)
         if (m.indptr[r + 1] < m.indptr[r]) return fail("CSR indptr decreases at row " + std::to_string(r));
     total_ = m.indptr[m.num_rows];
     if (total_ && (!m.indices || !m.values)) return fail("CSR arrays missing");
     row_nnz.assign(L_.num_rows, 0);
-    std::vector<uint32_t> indptr(size_t(L_.num_rows) + 1, uint32_t(total_));
-    for (uint32_t r = 0; r < m.num_rows; ++r) { indptr[r] = m.indptr[r]; row_nnz[r] = m.indptr[r + 1] - m.indptr[r]; }
+    indptr_rows_ = transposed_ ? m.num_rows : L_.num_rows;
+    std::vector<uint32_t> indptr(size_t(indptr_rows_) + 1, uint32_t(total_));
+    for (uint32_t r = 0; r < m.num_rows; ++r) {
+        indptr[r] = m.indptr[r];
+        if (!transposed_) row_nnz[r] = m.indptr[r + 1] - m.indptr[r];
+    }
     const size_t n = std::max<uint64_t>(total_, 1);
     bool ok = check(upload(d_indptr_, indptr, stream_), "upload indptr") && check(d_indices_.alloc_count(n), "hipMalloc(indices)") &&
               check(d_values_.alloc_count(n), "hipMalloc(values)") && check(d_scalar_.alloc(64), "hipMalloc") &&
@@ -776,6 +819,19 @@ bool GpuTiler::upload_csr(std::vector<uint32_t>& row_nnz) {
     if (ok && total_)
         ok = check(hipMemcpyAsync(d_indices_.get(), m.indices, size_t(total_) * 4, hipMemcpyHostToDevice, stream_), "upload indices") &&
              check(hipMemcpyAsync(d_values_.get(), m.values, size_t(total_) * 4, hipMemcpyHostToDevice, stream_), "upload values");
+    if (ok && transposed_ && total_) {
+        DeviceBuffer<uint32_t> d_rows;
+        ok = check(d_rows.alloc_count(L_.num_rows, 16), "hipMalloc(row counts)") &&
+             check(hipMemsetAsync(d_rows.get(), 0, size_t(L_.num_rows) * 4, stream_), "hipMemset(row counts)");
+        if (ok) {
+            hipLaunchKernelGGL(csr_transposed_row_counts_kernel, dim3(uint32_t((element_threads() + 255) / 256)), dim3(256), 0, stream_, d_indptr_.get(),
+                               d_indices_.get(), indptr_rows_, total_, m.num_cols, d_rows.get(), d_scalar_.get());
+            ok = check(hipGetLastError(), "csr_transposed_row_counts_kernel") &&
+                 check(hipMemcpyAsync(row_nnz.data(), d_rows.get(), size_t(L_.num_rows) * 4, hipMemcpyDeviceToHost, stream_), "read row counts") &&
+                 read_error("count rows", "count rows");      // (synchronises: `indptr` and d_rows are temporaries)
+        }
+        return ok;
+    }
     return ok && check(hipStreamSynchronize(stream_), "upload");      // `indptr` is a temporary
 }
 
@@ -856,8 +912,9 @@ bool GpuTiler::count_tiles(const std::vector<uint32_t>& block_of_row, uint32_t n
     if (!check(d_cnt.alloc_count(cnt.size(), 16), "hipMalloc")) return false;
     bool ok = check(hipMemsetAsync(d_cnt.get(), 0, cnt.size() * 4, stream_), "hipMemset");
     if (ok && csr_ && total_) {
-        hipLaunchKernelGGL(csr_count_tiles_kernel, dim3(uint32_t((element_threads() + 255) / 256)), dim3(256), 0, stream_, d_indptr_.get(), d_indices_.get(), L_.num_rows,
-                           total_, csr_->num_cols, uint32_t(geom_.logical_vb), d_block_of_row_.get(), tiles, S, L_.sub_width, d_cnt.get(), d_scalar_.get());
+        hipLaunchKernelGGL(transposed_ ? csr_count_tiles_kernel<true> : csr_count_tiles_kernel<false>, dim3(uint32_t((element_threads() + 255) / 256)), dim3(256), 0,
+                           stream_, d_indptr_.get(), d_indices_.get(), indptr_rows_, total_, csr_->num_cols, uint32_t(geom_.logical_vb), d_block_of_row_.get(), tiles, S,
+                           L_.sub_width, d_cnt.get(), d_scalar_.get());
         ok = check(hipGetLastError(), "csr_count_tiles_kernel") && read_error("count tiles", "count tiles");
     } else if (ok && total_slots_) {
         hipLaunchKernelGGL(count_tiles_kernel, dim3((total_slots_ + 255) / 256), dim3(256), 0, stream_, d_channels_.get(), groups<StreamGroup>(), num_groups_, total_slots_,
@@ -882,8 +939,10 @@ bool GpuTiler::sort_elements(const std::vector<uint32_t>& block_of_row, const st
               check(d_keys_in.alloc_count(n), "hipMalloc(keys)") && check(d_vals_in.alloc_count(n), "hipMalloc(values)") &&
               check(d_keys_.alloc_count(n), "hipMalloc(keys)") && check(d_vals_.alloc_count(n), "hipMalloc(values)");
     if (ok && csr_ && total_) {
-        hipLaunchKernelGGL(value_map_ ? csr_keys_kernel<true> : csr_keys_kernel<false>, dim3(uint32_t((element_threads() + 255) / 256)), dim3(256), 0, stream_,
-                           d_indptr_.get(), d_indices_.get(), d_values_.get(), L_.num_rows, total_, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED),
+        const auto keys_kernel_of = transposed_ ? (value_map_ ? csr_keys_kernel<true, true> : csr_keys_kernel<false, true>)
+                                                : (value_map_ ? csr_keys_kernel<true, false> : csr_keys_kernel<false, false>);
+        hipLaunchKernelGGL(keys_kernel_of, dim3(uint32_t((element_threads() + 255) / 256)), dim3(256), 0, stream_,
+                           d_indptr_.get(), d_indices_.get(), d_values_.get(), indptr_rows_, total_, uint32_t(geom_.logical_vb), uint32_t(geom_.impl == IMPL_FIXED),
                            d_block_of_row_.get(), d_row0.get(), d_unit_of.get(), tiles, S, L_.sub_width, d_keys_in.get(), d_vals_in.get());
         ok = check(hipGetLastError(), "csr_keys_kernel");
     } else if (ok && total_slots_) {

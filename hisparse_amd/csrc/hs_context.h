@@ -1,6 +1,6 @@
 // hs_context.h — the context behind the C-ABI of include/hisparse_hip.h, shared by its implementation files:
 //   hs_api.cpp     create / destroy, options, stream and binding hooks, enqueue, run / batch / partition / feedback / iterate, sync / read, timing
-//   hs_load.cpp    hs_load_matrix, hs_load_matrix_csr (+ autotune), hs_update_values, the debug reads
+//   hs_load.cpp    hs_load_matrix, hs_load_matrix_csr, hs_load_matrix_csr_transposed (+ autotune), hs_update_values, the debug reads
 //   hs_spmspv.cpp  the SpMSpV extension          hs_spmm.cpp  the SpMM extension
 // One context owns one HIP device, one stream and the device-resident data.  There is no CPU fallback anywhere in these files: without a
 // usable gfx950 device every call fails.

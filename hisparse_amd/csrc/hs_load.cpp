@@ -1,4 +1,4 @@
-// hs_load.cpp — hs_load_matrix (CPSR channel buffers) and hs_load_matrix_csr behind one body, the opt-in autotune around it,
+// hs_load.cpp — hs_load_matrix (CPSR channel buffers), hs_load_matrix_csr and hs_load_matrix_csr_transposed behind one body, the opt-in autotune around it,
 // hs_update_values and the debug reads of what a load left on the device (include/hisparse_hip.h).
 #include "hs_context.h"
 
@@ -88,21 +88,27 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
             // both products), but the device sort has no defined order among equal positions.  Do what a reference driver does instead:
             // format on the host (sw/benchmark.cpp:110-195) and hand the CPSR buffers to the host builder, like hs_load_matrix does for
             // such a matrix.
+            // (A transposed load formats A^T's own CSR, made on the host here: HostCsr, tiles_common.h.)
             start_over_on_host();
-            spmv::io::CSRMatrix<float> mat;
-            mat.num_rows = csr->num_rows;
-            mat.num_cols = csr->num_cols;
-            const uint64_t nnz = csr->indptr[csr->num_rows];
-            mat.adj_indptr.assign(csr->indptr, csr->indptr + csr->num_rows + 1);
-            mat.adj_indices.assign(csr->indices, csr->indices + nnz);
-            mat.adj_data.assign(csr->values, csr->values + nnz);
-            const hisparse::ChannelPackets packets = hisparse::format_matrix(mat, g, /*skip_empty_rows=*/true);
-            const void* chan[hisparse::NUM_HBM_CHANNELS];
-            uint64_t count[hisparse::NUM_HBM_CHANNELS];
-            for (uint32_t c = 0; c < hisparse::NUM_HBM_CHANNELS; ++c) { chan[c] = packets.channel[c].data(); count[c] = packets.channel[c].size(); }
+            const hisparse::dev::detail::HostCsr rows(csr);
             on_gpu = false;
-            ok = packets.num_rows == num_rows && packets.num_cols == num_cols &&
-                 hisparse::dev::build_stream_tiles(chan, count, g, num_rows, num_cols, num_row_partitions, num_col_partitions, uint32_t(ctx->compute_units), tiles, why);
+            if (rows.ok()) {      // (the device passes have checked every index already)
+                spmv::io::CSRMatrix<float> mat;
+                mat.num_rows = rows->num_rows;
+                mat.num_cols = rows->num_cols;
+                const uint64_t nnz = rows->indptr[rows->num_rows];
+                mat.adj_indptr.assign(rows->indptr, rows->indptr + rows->num_rows + 1);
+                mat.adj_indices.assign(rows->indices, rows->indices + nnz);
+                mat.adj_data.assign(rows->values, rows->values + nnz);
+                const hisparse::ChannelPackets packets = hisparse::format_matrix(mat, g, /*skip_empty_rows=*/true);
+                const void* chan[hisparse::NUM_HBM_CHANNELS];
+                uint64_t count[hisparse::NUM_HBM_CHANNELS];
+                for (uint32_t c = 0; c < hisparse::NUM_HBM_CHANNELS; ++c) { chan[c] = packets.channel[c].data(); count[c] = packets.channel[c].size(); }
+                ok = packets.num_rows == num_rows && packets.num_cols == num_cols &&
+                     hisparse::dev::build_stream_tiles(chan, count, g, num_rows, num_cols, num_row_partitions, num_col_partitions, uint32_t(ctx->compute_units), tiles, why);
+            } else {
+                why = "CSR column index outside the matrix";
+            }
         }
         if (!ok && !csr && on_gpu && why.rfind("gpu re-tile:", 0) == 0) {       // duplicates, or a HIP failure on the way: the host path decides
             start_over_on_host();
@@ -173,7 +179,7 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
     } else if (!map_on) {
         m.value_map_why = "the value_map option was off when the matrix was loaded";
     } else if (!csr) {
-        m.value_map_why = "the matrix came from hs_load_matrix (CPSR): only hs_load_matrix_csr keeps a value map";
+        m.value_map_why = "the matrix came from hs_load_matrix (CPSR): only hs_load_matrix_csr and hs_load_matrix_csr_transposed keep a value map";
     } else if (!image_on_device) {
         m.value_map_why = "the image was built by the host builder (duplicate (row, column) entries, bitmap_build=host, or SWEEP chunks spanning more than 65535 "
                           "columns): it has no value map";
@@ -320,6 +326,32 @@ int update_values(hs_context* ctx, const float* values, uint64_t nnz, bool from_
     return HS_OK;
 }
 
+// hs_load_matrix_csr and hs_load_matrix_csr_transposed: the arrays describe a num_rows x num_cols matrix A; the context gets A, or A^T
+int load_csr(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, const float* values, bool transposed,
+             uint32_t* padded_rows, uint32_t* padded_cols) {
+    if (!ctx || !indptr) return fail(ctx, HS_ERR_BAD_ARG, "null argument");
+    const Geometry& g = ctx->geom;
+    if (num_rows == 0 || num_cols == 0) return fail(ctx, HS_ERR_BAD_ARG, "empty matrix");
+    hisparse::dev::CsrView view;
+    view.num_rows = num_rows;
+    view.num_cols = num_cols;
+    view.indptr = indptr;
+    view.indices = indices;
+    view.values = values;
+    view.transposed = transposed;
+    // util_round_csr_matrix_dim (sw/data_formatter.h:15-29): rows up to a multiple of P*C*F, columns to a multiple of 8
+    const uint64_t rows = (uint64_t(view.out_rows()) + g.row_divisor - 1) / g.row_divisor * g.row_divisor;
+    const uint64_t cols = (uint64_t(view.out_cols()) + hisparse::PACK_SIZE - 1) / hisparse::PACK_SIZE * hisparse::PACK_SIZE;
+    if (rows > 0xffffffffull || cols > 0xffffffffull) return fail(ctx, HS_ERR_BAD_ARG, "padded dimensions exceed 32 bits");
+    const int rc = load_matrix_impl(ctx, nullptr, nullptr, &view, uint32_t(rows), uint32_t(cols), uint32_t((rows + g.logical_ob - 1) / g.logical_ob),
+                                    uint32_t((cols + g.logical_vb - 1) / g.logical_vb));
+    if (rc == HS_OK) {
+        if (padded_rows) *padded_rows = uint32_t(rows);
+        if (padded_cols) *padded_cols = uint32_t(cols);
+    }
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -332,26 +364,12 @@ int hs_load_matrix(hs_context* ctx, const void* const channel[HS_NUM_CHANNELS], 
 
 int hs_load_matrix_csr(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, const float* values,
                        uint32_t* padded_rows, uint32_t* padded_cols) {
-    if (!ctx || !indptr) return fail(ctx, HS_ERR_BAD_ARG, "null argument");
-    const Geometry& g = ctx->geom;
-    if (num_rows == 0 || num_cols == 0) return fail(ctx, HS_ERR_BAD_ARG, "empty matrix");
-    // util_round_csr_matrix_dim (sw/data_formatter.h:15-29): rows up to a multiple of P*C*F, columns to a multiple of 8
-    const uint64_t rows = (uint64_t(num_rows) + g.row_divisor - 1) / g.row_divisor * g.row_divisor;
-    const uint64_t cols = (uint64_t(num_cols) + hisparse::PACK_SIZE - 1) / hisparse::PACK_SIZE * hisparse::PACK_SIZE;
-    if (rows > 0xffffffffull || cols > 0xffffffffull) return fail(ctx, HS_ERR_BAD_ARG, "padded dimensions exceed 32 bits");
-    hisparse::dev::CsrView view;
-    view.num_rows = num_rows;
-    view.num_cols = num_cols;
-    view.indptr = indptr;
-    view.indices = indices;
-    view.values = values;
-    const int rc = load_matrix_impl(ctx, nullptr, nullptr, &view, uint32_t(rows), uint32_t(cols), uint32_t((rows + g.logical_ob - 1) / g.logical_ob),
-                                    uint32_t((cols + g.logical_vb - 1) / g.logical_vb));
-    if (rc == HS_OK) {
-        if (padded_rows) *padded_rows = uint32_t(rows);
-        if (padded_cols) *padded_cols = uint32_t(cols);
-    }
-    return rc;
+    return load_csr(ctx, num_rows, num_cols, indptr, indices, values, false, padded_rows, padded_cols);
+}
+
+int hs_load_matrix_csr_transposed(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, const float* values,
+                                  uint32_t* padded_rows, uint32_t* padded_cols) {
+    return load_csr(ctx, num_rows, num_cols, indptr, indices, values, true, padded_rows, padded_cols);
 }
 
 int hs_update_values(hs_context* ctx, const float* values, uint64_t nnz) { return update_values(ctx, values, nnz, true); }

@@ -368,6 +368,12 @@ struct CsrView {
     const uint32_t* indices = nullptr;
     const float* values = nullptr;
     bool value_map = false;                  // option value_map: the device builder also records every non-zero's value word index (gpu_tiles.h)
+    // hs_load_matrix_csr_transposed: the fields above describe the ARRAYS (a matrix A); the matrix to build is A^T, num_cols x num_rows.
+    // The device builder swaps the roles of row and column element by element (gpu_tiles.h), no transposed copy exists; a value map
+    // stays in the order of the arrays.  A host builder sees A^T's own CSR through detail::HostCsr (tiles_common.h).
+    bool transposed = false;
+    uint32_t out_rows() const { return transposed ? num_cols : num_rows; }      // of the matrix to build, not yet rounded up
+    uint32_t out_cols() const { return transposed ? num_rows : num_cols; }
 };
 
 // Decode + validate + re-tile.  `max_workgroups` = workgroups the device keeps resident (one per CU).

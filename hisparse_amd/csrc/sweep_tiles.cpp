@@ -90,7 +90,7 @@ double sweep_plan(const Layout& L, uint64_t nnz, uint32_t max_workgroups, uint32
 }
 
 bool build_sweep_tiles(const Layout& L, const void* const channel[NUM_HBM_CHANNELS], const uint64_t n_packets[NUM_HBM_CHANNELS],
-                       const std::vector<uint32_t>& row_nnz, uint32_t max_workgroups, StreamTiles& out, std::string& error, const CsrView* csr,
+                       const std::vector<uint32_t>& row_nnz, uint32_t max_workgroups, StreamTiles& out, std::string& error, const CsrView* csr_in,
                        GpuTiler* gpu, uint64_t image_slack) {
     const uint32_t num_rows = L.num_rows, num_cols = L.num_cols, RP = L.row_parts, CP = L.col_parts;
     const uint32_t G = std::max<uint32_t>(1, max_workgroups);
@@ -108,7 +108,9 @@ bool build_sweep_tiles(const Layout& L, const void* const channel[NUM_HBM_CHANNE
     if (elems) return true;
     elems_buf.reset(new uint64_t[std::max<uint64_t>(nnz, 1)]);
     elems = elems_buf.get();
-    if (csr) {              // value words as csr_matrix_convert_from_float gives them (sw/data_loader.h:76-84)
+    if (csr_in) {           // value words as csr_matrix_convert_from_float gives them (sw/data_loader.h:76-84)
+        const HostCsr csr(csr_in);      // (a transposed load: A^T's rows, made here)
+        if (!csr.ok()) { error = "CSR column index outside the matrix"; return false; }
         const bool fixed = L.g->impl == IMPL_FIXED;
         std::atomic<bool> bad_column(false);
         parallel_for((csr->num_rows + 1023) / 1024, [&](size_t piece) {

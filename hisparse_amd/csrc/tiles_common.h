@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "hisparse/data_loader.h"
 #include "hisparse/worker_pool.h"
 #include "stream_tiles.h"
 
@@ -417,6 +418,44 @@ inline void build_row_ranges_at_most(const Layout& L, const std::vector<uint32_t
         target += std::max<uint64_t>(1, target / 128);
     }
 }
+
+// The CSR rows a HOST builder reads.  A plain CsrView passes through.  A transposed one (hs_load_matrix_csr_transposed) is materialised
+// here as A^T's own CSR by the counting-sort csr2csc of hisparse/data_loader.h (the CSC of A is the CSR of A^T; rows of A stay ascending
+// inside a column, as in scipy's .T.tocsr()), and the host builder goes on as for a plain load.  ok() is false when an index lies
+// outside the matrix (csr2csc indexes a table by it).
+class HostCsr {
+  public:
+    explicit HostCsr(const CsrView* csr) : view_(csr) {
+        if (!csr || !csr->transposed) return;
+        const uint64_t nnz = csr->indptr[csr->num_rows];
+        for (uint64_t e = 0; e < nnz; ++e)
+            if (csr->indices[e] >= csr->num_cols) { ok_ = false; return; }
+        spmv::io::CSRMatrix<float> a;
+        a.num_rows = csr->num_rows;
+        a.num_cols = csr->num_cols;
+        a.adj_indptr.assign(csr->indptr, csr->indptr + csr->num_rows + 1);
+        a.adj_indices.assign(csr->indices, csr->indices + nnz);
+        a.adj_data.assign(csr->values, csr->values + nnz);
+        t_ = spmv::io::csr2csc(a);
+        own_.num_rows = csr->num_cols;
+        own_.num_cols = csr->num_rows;
+        own_.indptr = t_.adj_indptr.data();
+        own_.indices = t_.adj_indices.data();
+        own_.values = t_.adj_data.data();
+        view_ = &own_;
+    }
+    HostCsr(const HostCsr&) = delete;
+    HostCsr& operator=(const HostCsr&) = delete;
+    bool ok() const { return ok_; }
+    const CsrView* operator->() const { return view_; }
+    explicit operator bool() const { return view_ != nullptr; }
+
+  private:
+    const CsrView* view_;
+    CsrView own_;
+    spmv::io::CSCMatrix<float> t_;
+    bool ok_ = true;
+};
 
 }  // namespace detail
 

@@ -17,7 +17,7 @@ _lib = None
 
 EXPORTS = [
     "hs_strerror", "hs_last_error", "hs_create", "hs_destroy", "hs_load_matrix", "hs_load_vector", "hs_run",
-    "hs_load_matrix_csr", "hs_run_batch", "hs_run_partition", "hs_sync", "hs_read_result", "hs_set_stream", "hs_get_stream", "hs_device_vector", "hs_device_result",
+    "hs_load_matrix_csr", "hs_load_matrix_csr_transposed", "hs_run_batch", "hs_run_partition", "hs_sync", "hs_read_result", "hs_set_stream", "hs_get_stream", "hs_device_vector", "hs_device_result",
     "hs_bind_device_vector", "hs_bind_device_result", "hs_push_result", "hs_set_option", "hs_feedback", "hs_iterate", "hs_load_matrix_csc", "hs_spmspv", "hs_spmspv_device", "hs_read_spmspv_result", "hs_spmspv_status", "hs_spmm", "hs_spmm_device", "hs_get_stats", "hs_time_runs", "hs_time_kernel", "hs_debug_read_tiles", "hs_debug_read_mfma_image", "hs_update_values", "hs_update_values_device", "hs_tiles_build", "hs_tiles_info",
     "hs_tiles_copy", "hs_tiles_free", "hs_tiles_last_error",
 ]
@@ -91,6 +91,7 @@ def lib():
         l.hs_debug_read_tiles.argtypes = [vp, vp, u64, vp, vp]
         l.hs_debug_read_mfma_image.argtypes = [vp, vp, u64, C.POINTER(u64)]
         l.hs_load_matrix_csr.argtypes = [vp, u32, u32, vp, vp, vp, C.POINTER(u32), C.POINTER(u32)]
+        l.hs_load_matrix_csr_transposed.argtypes = l.hs_load_matrix_csr.argtypes
         l.hs_spmm.argtypes = [vp, vp, u32, u32, vp, u32]
         l.hs_spmm_device.argtypes = [vp, vp, u64, vp, u64, u32]
         l.hs_update_values.argtypes = [vp, vp, u64]
@@ -174,9 +175,11 @@ class SpmvEngine:
         self.num_rows, self.num_cols = num_rows, num_cols
         self.row_parts, self.col_parts = num_row_partitions, num_col_partitions
 
-    def load_matrix_csr(self, csr):
+    def load_matrix_csr(self, csr, transpose=False):
         """Straight from a host.CSRMatrix (or (num_rows, num_cols, indptr, indices, data) arrays) without csr2cpsr: the device pads,
-        converts and re-tiles (hs_load_matrix_csr).  Sets num_rows / num_cols to the padded dimensions x and y then have."""
+        converts and re-tiles (hs_load_matrix_csr).  Sets num_rows / num_cols to the padded dimensions x and y then have.
+        transpose=True (hs_load_matrix_csr_transposed): the arrays describe A, the engine holds A^T -- the image of the host-transposed
+        matrix, without transposing; update_values keeps taking the values in the order of the arrays given here."""
         if isinstance(csr, host.CSRMatrix):
             rows, cols = csr.num_rows, csr.num_cols
             indptr, indices, data = csr.arrays()
@@ -185,8 +188,9 @@ class SpmvEngine:
         indptr, indices = (np.ascontiguousarray(a, dtype=np.uint32) for a in (indptr, indices))
         data = np.ascontiguousarray(data, dtype=np.float32)
         pr, pc = C.c_uint32(), C.c_uint32()
-        self._check(lib().hs_load_matrix_csr(self._h, rows, cols, indptr.ctypes.data, indices.ctypes.data if indices.size else None,
-                                             data.ctypes.data if data.size else None, C.byref(pr), C.byref(pc)))
+        load = lib().hs_load_matrix_csr_transposed if transpose else lib().hs_load_matrix_csr
+        self._check(load(self._h, rows, cols, indptr.ctypes.data, indices.ctypes.data if indices.size else None,
+                         data.ctypes.data if data.size else None, C.byref(pr), C.byref(pc)))
         self.num_rows, self.num_cols = pr.value, pc.value
         self.row_parts, self.col_parts = -(-pr.value // (128 * self.ob_bank)), -(-pc.value // (8 * self.vb_bank))
         self.csr_nnz = int(indptr[rows]) if indptr.size > rows else 0

@@ -251,15 +251,38 @@ int hs_spmspv_status(hs_context* ctx, uint32_t* overflowed, void** overflow_word
 int hs_load_matrix_csr(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, const float* values,
                        uint32_t* padded_rows, uint32_t* padded_cols);
 
+/* ---- load A^T from A's CSR (EXTENSION; no reference counterpart) ---------------------------------------------------------------------
+ * The callers hs_update_values serves need the other product too: g_x = W^T g_y next to y = W x, A^T v in BiCG and LSQR, the edges walked
+ * backwards in HITS and reverse PageRank.  num_rows, num_cols, indptr[num_rows + 1], indices and values describe A exactly as for
+ * hs_load_matrix_csr; the context then holds A^T, which is num_cols x num_rows: padded_rows = num_cols rounded up to the context's row
+ * divisor (128 * interleave), padded_cols = num_rows rounded up to 8, and hs_load_vector / hs_read_result expect those.  No transposed
+ * copy is made: the device builder reads every element of the arrays as (row = indices[e], column = the row that holds e).
+ * CONTRACT: the device image, Block[], Unit[], the matrix-engine image and hs_stats (apart from load_seconds) equal, byte for byte, what
+ * hs_load_matrix_csr leaves for the host-transposed arrays of the same matrix (rows of A ascending inside a column of A: scipy's
+ * .T.tocsr(), hsf_csr_to_csc, csr2csc).  A^T is an ordinary image, so every parity and float-contract statement and every entry point
+ * (hs_run, hs_run_batch, hs_iterate, hs_spmm*, hs_push_result) carries over unchanged.
+ * VALUE ORDER: with value_map = 1 the map follows the order of the arrays PASSED IN, A's order.  hs_update_values / hs_update_values_device
+ * on this context take the same `values` array, with the same nnz check, as a context that loaded the same arrays with hs_load_matrix_csr:
+ * one device array of values refreshes the forward and the backward context with two calls and no permutation.
+ * A matrix held in CSC form is the CSR of its transpose: passing CSC arrays (num_rows = its column count, num_cols = its row count,
+ * indptr over its columns, indices = its row indices) loads that matrix itself.
+ * Everything else is hs_load_matrix_csr: autotune, forced formats, spmm_vectors, col_slices, LIGHT, error codes, "replaces any previously
+ * loaded matrix".  An index >= num_cols, an indptr that decreases or does not start at 0: HS_ERR_BAD_MATRIX, the context stays usable.
+ * Where the plain load goes to a host builder (a (row, column) twice, bitmap_build=host, SWEEP chunks the device builder gives up on) this
+ * one first materialises A^T's CSR on the host (csr2csc, hisparse/data_loader.h) and goes on as the plain load does: duplicates still add
+ * up, and such an image has no value map (hs_update_values says why, as above). */
+int hs_load_matrix_csr_transposed(hs_context* ctx, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, const float* values,
+                                  uint32_t* padded_rows, uint32_t* padded_cols);
+
 /* ---- value update (EXTENSION: same sparsity pattern, new numbers; no reference counterpart) ----------------------------------------
  * A load plans the tiles, sorts every non-zero and emits the image -- tens of milliseconds on the large matrices, hundreds of SpMVs.  A
  * caller that keeps the pattern and changes only the values (pruned layers during fine-tuning, re-weighted graphs, solvers whose
  * coefficients change) refreshes the values in place instead:
- *   hs_set_option "value_map" = 1 (plan-time; environment HISPARSE_VALUE_MAP) before hs_load_matrix_csr: the load keeps a VALUE MAP on the
+ *   hs_set_option "value_map" = 1 (plan-time; environment HISPARSE_VALUE_MAP) before hs_load_matrix_csr(_transposed): the load keeps a VALUE MAP on the
  *     device -- per non-zero, in the order of the CSR arrays, the 32-bit word index of its value in the image (4 bytes per non-zero; a float
  *     BITMAP matrix with the matrix-engine image of hs_spmm keeps a second one, 8 bytes per non-zero in all).  The load itself costs 4 bytes
  *     per non-zero more while it sorts.  Option 0 (the default): the load is what it always was.  Under autotune only the kept image gets a map.
- *   hs_update_values: `values` in HOST memory, nnz floats in the non-zero order of the CSR arrays of the last hs_load_matrix_csr (nnz =
+ *   hs_update_values: `values` in HOST memory, nnz floats in the non-zero order of the CSR arrays of the last hs_load_matrix_csr or hs_load_matrix_csr_transposed (nnz =
  *     its indptr[num_rows], before padding), converted like csr_matrix_convert_from_float as the load converts them.  Copied into a device
  *     staging buffer of the context (allocated on first use, freed with the matrix), then one kernel scatters the value words into the
  *     image; returns once `values` may be reused (as hs_load_vector).
