@@ -1,6 +1,6 @@
 // gpu_tiles.h — the data-touching passes of the load-time re-tiling, on the GPU.
 //
-// stream_tiles.cpp keeps ALL the planning (format, tile plan, row ranges, column slices, stream layout, workgroup assignment: small,
+// stream_tiles.cpp keeps ALL the planning (stream_plan.h: format, tile plan; TileBuild: row ranges, column slices, stream layout, workgroup assignment: small,
 // sequential, a few milliseconds) and asks a "source" for the six things that touch every non-zero:
 //     rows' non-zero counts  ->  (row range, sub-tile) counts  ->  every unit's elements sorted by position
 //     ->  DELTA slot counts / OWNER shares  ->  the emitted image.
@@ -51,7 +51,7 @@ class GpuTiler {
     // totals per (row range, column partition, sub-tile): cnt[(b * CP + cp) * S + s]
     bool count_tiles(const std::vector<uint32_t>& block_of_row, uint32_t num_ranges, std::vector<uint32_t>& cnt);
     // Every unit's elements sorted by position, unit u at [plans[u].scratch, + plans[u].n) of the device arrays.  unit_of as in
-    // stream_tiles.cpp ((range, cp, s) -> unit or 0xffffffff); row0 of every range.  `duplicates` = some (row, column) occurs twice
+    // stream_tiles.cpp: TileBuild::enumerate_blocks ((range, cp, s) -> unit or 0xffffffff); row0 of every range.  `duplicates` = some (row, column) occurs twice
     // (the host's order among equal positions is by value word; the caller falls back to the host builder then).
     bool sort_elements(const std::vector<uint32_t>& block_of_row, const std::vector<uint32_t>& range_row0, const std::vector<uint32_t>& unit_of,
                        const std::vector<detail::UnitPlan>& plans, bool& duplicates);

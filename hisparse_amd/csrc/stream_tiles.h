@@ -48,7 +48,7 @@
 //     DELTA is tried when the mean position gap rows*cols/nnz lies in [kDeltaMinMeanGap, kDeltaMaxMeanGap] (hyper-sparse matrices
 //     would need a bridge for every other gap) and kept when, after the sort, it needs at most 5 % bridge slots AND saves more
 //     than kDeltaMinSavedBytes of stream against PAIRS: its slots cost more instructions and a head record per unit and
-//     wavefront, which only pays when the stream bounds the kernel (stream_tiles.cpp has the measurements).  Inside a DELTA matrix,
+//     wavefront, which only pays when the stream bounds the kernel (stream_plan.h: delta_or_pairs has the measurements).  Inside a DELTA matrix,
 //     blocks whose rows are long (block gap < kDenseMeanGap) are flagged kBlockDenseRows: there every lane sums its run in a
 //     register and touches its LDS accumulator only when its row changes (otherwise the lanes of one instruction collide on
 //     the few rows there are: 55.6 vs 38.9 us on mouse_gene).
@@ -91,7 +91,7 @@ constexpr uint32_t kMaxSweepSlices = 16;      // SWEEP images (round 5): a short
 // middle (profiles/r06_carry_mid_size.txt, alternating runs): gplus (87 MB) 19.9 -> 19.3 us, one rank's slab of mouse_gene split 2 ways (89 MB) 20.2 -> 19.4,
 // of hollywood split 8 ways (SWEEP, 113 MB) 24.6 -> 24.1, of ogbl-ppa split 2 ways (155 MB) 32.2 -> 31.4: carried up to 160 MiB.
 constexpr uint64_t kCarryMaxImageBytes = 160ull << 20;
-constexpr uint64_t kSlicedDeltaMaxImageBytes = 48ull << 20;   // the sliced DELTA plan of fixed-point dense layers (stream_tiles.cpp): measured up to 8.5 M non-zeros, no further
+constexpr uint64_t kSlicedDeltaMaxImageBytes = 48ull << 20;   // the sliced DELTA plan of fixed-point dense layers (stream_plan.h: choose_dense_rows): measured up to 8.5 M non-zeros, no further
 constexpr uint64_t kResidentMaxImageBytes = 256ull << 20;   // SWEEP images up to the size of the Infinity Cache are streamed without the non-temporal hint (plan_stream_resident below)
 // Row-block (PAIRS / DELTA) images, round 6 (profiles/r06_rowblock_stream_policy*.txt): without `nt` where the image fits the Infinity Cache AND its blocks walk
 // several units.  Measured to gain a little even above the cache (ogbl-ppa, 267 MiB: -1.5 % warm) -- but an image that does not fit is evicted between
@@ -118,7 +118,7 @@ constexpr uint32_t kBridgeAdvance = 0xffffu;                  // ... which advan
 constexpr double kDeltaMinMeanGap = 8.0;                      // (denser matrices are BITMAP candidates)
 constexpr double kDeltaMaxMeanGap = 20000.0;                  // sparser matrices: > 4 % of the gaps need bridges, PAIRS wins
 constexpr uint64_t kDeltaMinSavedBytes = 23u << 20;           // DELTA must save this much stream against PAIRS (3.5 us at 6.5 TB/s) ...
-constexpr uint64_t kDeltaMinSavedBytesFloat = 40u << 20;      // ... 6 us in the float modes (stream_tiles.cpp: the choice after the sort)
+constexpr uint64_t kDeltaMinSavedBytesFloat = 40u << 20;      // ... 6 us in the float modes (stream_plan.h: delta_or_pairs, the choice after the sort)
 constexpr double kDenseMeanGap = 320.0;                       // DELTA blocks denser than this (>= 24 elements per row and sub-tile) sum per lane in registers (kBlockDenseRows);
                                                               // sparser ones lose with it (400000 x 100000, gap 512: 89.8 vs 83.2 us), denser ones win big (40000^2, gap 64: 34.5 vs 53.0)
 enum StreamFormat : uint32_t { kFormatPairs = 0, kFormatDelta = 1, kFormatBitmap = 2, kFormatOwner = 3, kFormatPairs24 = 4, kFormatOwner24 = 5, kFormatSweep = 6 };
@@ -242,14 +242,14 @@ constexpr uint32_t kSweepMaxBlockRowsFloat = kMaxLdsBytes / kAccumulatorBytes - 
 constexpr uint32_t kSweepMaxBlockRowsFixed = (kMaxLdsBytes / 4 - 2) * 32 / 33 - 1;                // 39716: (rows + 1) x 4 bytes + (rows + 32) / 32 x 4 bytes <= 160 KiB
 constexpr uint32_t kSweepColAlign = 32;                       // slices start on a 128-byte line of x
 // Chosen (unforced) where OWNER24 would be (mean position gap rows x cols / nnz above kOwnerMinMeanGap, more than kSweepMinNnz non-zeros) and its
-// plan is modelled faster (stream_tiles.cpp: "SWEEP"): OWNER24 pays per (row range x sub-tile) unit whatever the unit holds, SWEEP per element
+// plan is modelled faster (stream_plan.h: choose_sweep): OWNER24 pays per (row range x sub-tile) unit whatever the unit holds, SWEEP per element
 // and per line of x.  For square power-law matrices that comes out as a mean gap of ~60 K in fixed point, ~70 K in the float modes.  Measured on power-law squares of 1.0 / 1.6 / 2.4 M rows (tools/probe_sweep.py,
 // profiles/r04_sweep_vs_owner_synthetic.txt), whole step, SWEEP against OWNER24: gap 50 K +3 ... -3 % (fixed) / +5 ... +11 % (float), 70 K -6 ...
 // -13 % / +2 ... -7 %, 100 K -12 ... -24 % / -3 ... -20 %, 200 K -20 ... -38 % in both; pokec (gap 87 K) 95.5 -> 78.0 us fixed, 122.6 -> 88.3 us
 // float_pob; ogbn-products (48 K) stays OWNER24 (204 against 216 us).
-constexpr double kSweepSlabMinMeanGap = 8000.0;                // short, wide fixed-point slabs that fit the Infinity Cache take SWEEP from this mean gap on (stream_tiles.cpp)
+constexpr double kSweepSlabMinMeanGap = 8000.0;                // short, wide fixed-point slabs that fit the Infinity Cache take SWEEP from this mean gap on (stream_plan.h: choose_sweep)
 constexpr uint64_t kSweepMinNnz = (2u << 20) + 1;             // smaller matrices: the LIGHT plan's (when x is short) or the row-block kernel's
-constexpr uint64_t kFloatOneSliceOwnerMinNnz = 8u << 20;         // float modes: a one-slice PAIRS-family plan of at least this many non-zeros is planned again as OWNER24 (stream_tiles.cpp, round 6)
+constexpr uint64_t kFloatOneSliceOwnerMinNnz = 8u << 20;         // float modes: a one-slice PAIRS-family plan of at least this many non-zeros is planned again as OWNER24 (stream_plan.h: plan_row_blocks, round 6)
 constexpr uint64_t kSweepMinNnzWide = 256u << 10;             // ... unless x is wider than the LIGHT plan takes (kLightMaxUnits sub-tiles): SWEEP from here on (round 6)
 constexpr uint32_t kDenseBlockRows = 32;                      // blocks with at most this many rows use the dense-row layout
 constexpr uint32_t kBlockDenseRows = 1u;                      // Block::flags bit

@@ -3,7 +3,6 @@
 #include "tiles_common.h"
 #include "gpu_tiles.h"
 namespace hisparse { namespace dev {
-GpuTiler::~GpuTiler() {}
 GpuTiler::GpuTiler(const detail::Layout&, const void* const[NUM_HBM_CHANNELS], const uint64_t[NUM_HBM_CHANNELS], hipStream_t) {}
 GpuTiler::GpuTiler(const detail::Layout&, const CsrView&, hipStream_t) {}
 bool GpuTiler::count_rows(std::vector<uint32_t>&, uint64_t&) { return false; }
