@@ -345,7 +345,10 @@ bool build_bitmap_tiles(const Layout& L, const void* const channel[NUM_HBM_CHANN
             const double cost = rounds * (chunk + 1.5) * (1.0 + 0.7 / rounds);
             if (cost < best_cost) { best_cost = cost; mi.chunk = chunk; }
         }
-        if (const char* force = env_switch("HISPARSE_MFMA_CHUNK")) mi.chunk = std::max(1, std::atoi(force));      // experiments
+        // (experiments; a unit of GR groups or more is the whole row.  Out of range: refused, tiles_common.h)
+        if (const char* force = env_switch("HISPARSE_MFMA_CHUNK")) {
+            if (!parse_mfma_chunk(force, mi.chunk)) { error = kBadMfmaChunk; out.mfma = MfmaImage(); return false; }
+        }
         mi.chunks = ((GR + mi.chunk - 1) / mi.chunk + 3) / 4 * 4;
         const uint64_t mask_words = uint64_t(mi.tiles) * GR * kMfmaTileRows * 2;
         mi.offsets_word = mask_words;

@@ -406,6 +406,10 @@ int hs_set_option(hs_context* ctx, const char* key, const char* value) {
     if (k == "ABLATE" || k == "DEPTH" || k == "TIMELINE_OUT")
         return fail(ctx, HS_ERR_BAD_ARG, "'" + k + "' is a profiling switch of libhisparse_hip_prof.so (wrong results by design), not an option of this library");
     if (!known) return fail(ctx, HS_ERR_BAD_ARG, "unknown option '" + std::string(key) + "'");
+    if (value && *value && k == "MFMA_CHUNK") {      // a value the kernel cannot take is refused here, not clamped at the load
+        uint32_t chunk = 0;
+        if (!hisparse::dev::detail::parse_mfma_chunk(value, chunk)) return fail(ctx, HS_ERR_BAD_ARG, hisparse::dev::detail::kBadMfmaChunk);
+    }
     if (value && *value) ctx->options["HISPARSE_" + k] = value;
     else ctx->options.erase("HISPARSE_" + k);
     drop_batch_graph(ctx);      // the captured batch bakes in whatever enqueue() read at capture time: any option change invalidates it

@@ -116,7 +116,7 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
             ok = hisparse::dev::build_stream_tiles(channel, n_packets, g, num_rows, num_cols, num_row_partitions, num_col_partitions,
                                                    uint32_t(ctx->compute_units), tiles, why);
         }
-        if (!ok) rc = fail(ctx, HS_ERR_BAD_MATRIX, why);
+        if (!ok) rc = fail(ctx, why == hisparse::dev::detail::kBadMfmaChunk ? HS_ERR_BAD_ARG : HS_ERR_BAD_MATRIX, why);      // (an option of the environment the load cannot take)
     } catch (const std::bad_alloc&) {
         rc = fail(ctx, HS_ERR_NO_MEMORY, "out of host memory while re-tiling the matrix");
     } catch (const std::exception& e) {      // whatever a builder task threw (WorkerPool rethrows it): never through the C ABI

@@ -6,6 +6,7 @@
 
 #include "hisparse_hip.h"
 #include "stream_tiles.h"
+#include "tiles_common.h"
 
 struct hs_tiles {
     hisparse::dev::StreamTiles t;
@@ -32,7 +33,7 @@ int hs_tiles_build(const void* const channel[HS_NUM_CHANNELS], const uint64_t n_
         if (!hisparse::dev::build_stream_tiles(channel, n_packets, hisparse::make_geometry(impl, ob_bank, vb_bank), num_rows, num_cols,
                                                num_row_partitions, num_col_partitions, max_workgroups, h->t, g_tiles_error)) {
             delete h;
-            return HS_ERR_BAD_MATRIX;
+            return g_tiles_error == hisparse::dev::detail::kBadMfmaChunk ? HS_ERR_BAD_ARG : HS_ERR_BAD_MATRIX;
         }
     } catch (const std::bad_alloc&) {
         delete h;
@@ -67,6 +68,19 @@ int hs_tiles_copy(const hs_tiles* h, void* image, void* blocks, void* units, uin
     if (units && !h->t.units.empty()) std::memcpy(units, h->t.units.data(), h->t.units.size() * sizeof(hisparse::dev::Unit));
     if (wg_first) std::memcpy(wg_first, h->t.wg_first.data(), h->t.wg_first.size() * sizeof(uint32_t));
     if (block_order && !h->t.block_order.empty()) std::memcpy(block_order, h->t.block_order.data(), h->t.block_order.size() * sizeof(uint32_t));
+    return HS_OK;
+}
+
+int hs_tiles_mfma(const hs_tiles* h, void* words, uint64_t capacity, uint64_t* bytes, uint32_t* chunk, uint32_t* chunks) {
+    if (!h) return HS_ERR_BAD_ARG;
+    const hisparse::dev::MfmaImage& mi = h->t.mfma;
+    if (bytes) *bytes = mi.words.size();
+    if (chunk) *chunk = mi.chunk;
+    if (chunks) *chunks = mi.chunks;
+    if (words) {
+        if (capacity < mi.words.size()) return HS_ERR_BAD_ARG;
+        if (!mi.words.empty()) std::memcpy(words, mi.words.data(), mi.words.size());
+    }
     return HS_OK;
 }
 

@@ -62,6 +62,24 @@ inline const char* option_lookup(const OptionMap* options, const char* name) {
 }
 inline const char* env_switch(const char* name) { return option_lookup(active_options(), name); }
 
+// mfma_chunk (groups per wavefront unit of the matrix engine's image): a whole number 1 ... 65536, nothing behind it.  A unit of all the
+// groups of a row or more is the whole row (the kernel cuts every unit at the row's end); beyond the cap the kernel's 32-bit unit x chunk
+// would wrap (1431655766 x 3 = 2: unit 3 of a tile would begin again at group 2), and std::atoi of a longer number is undefined.
+constexpr uint32_t kMaxMfmaChunk = 65536;
+inline const char* const kBadMfmaChunk = "HISPARSE_MFMA_CHUNK must be a whole number from 1 to 65536";
+inline bool parse_mfma_chunk(const char* text, uint32_t& chunk) {
+    if (!text || *text < '0' || *text > '9') return false;
+    uint64_t v = 0;
+    for (const char* p = text; *p; ++p) {
+        if (*p < '0' || *p > '9') return false;
+        v = v * 10 + uint64_t(*p - '0');
+        if (v > kMaxMfmaChunk) return false;
+    }
+    if (v == 0) return false;
+    chunk = uint32_t(v);
+    return true;
+}
+
 struct PhaseTimer {   // HISPARSE_PLAN_DEBUG=1: wall time of the load-time passes
     const bool on = env_switch("HISPARSE_PLAN_DEBUG") != nullptr;
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();

@@ -19,7 +19,7 @@ EXPORTS = [
     "hs_strerror", "hs_last_error", "hs_create", "hs_destroy", "hs_load_matrix", "hs_load_vector", "hs_run",
     "hs_load_matrix_csr", "hs_load_matrix_csr_transposed", "hs_run_batch", "hs_run_partition", "hs_sync", "hs_read_result", "hs_set_stream", "hs_get_stream", "hs_device_vector", "hs_device_result",
     "hs_bind_device_vector", "hs_bind_device_result", "hs_push_result", "hs_set_option", "hs_feedback", "hs_iterate", "hs_load_matrix_csc", "hs_spmspv", "hs_spmspv_device", "hs_read_spmspv_result", "hs_spmspv_status", "hs_spmm", "hs_spmm_device", "hs_get_stats", "hs_time_runs", "hs_time_kernel", "hs_debug_read_tiles", "hs_debug_read_mfma_image", "hs_update_values", "hs_update_values_device", "hs_tiles_build", "hs_tiles_info",
-    "hs_tiles_copy", "hs_tiles_free", "hs_tiles_last_error",
+    "hs_tiles_copy", "hs_tiles_mfma", "hs_tiles_free", "hs_tiles_last_error",
 ]
 
 
@@ -103,6 +103,7 @@ def lib():
             l.hs_tiles_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u64),
                                         C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
             l.hs_tiles_copy.argtypes = [vp, vp, vp, vp, vp, vp]
+            l.hs_tiles_mfma.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32)]
             l.hs_tiles_free.argtypes = [vp]
             l.hs_tiles_free.restype = None
             l.hs_tiles_last_error.restype = C.c_char_p
@@ -364,7 +365,8 @@ class SpmvEngine:
 
 
 def build_tiles(packets, impl, ob_bank, vb_bank, num_rows, num_cols, num_row_partitions, num_col_partitions, max_workgroups):
-    """What hs_load_matrix would upload (no GPU involved): dict(image, blocks, units, wg_first, block_order, ...)."""
+    """What hs_load_matrix would upload (no GPU involved): dict(image, blocks, units, wg_first, block_order, ..., mfma: the second image
+    of a float BITMAP matrix as bytes, empty when there is none, mfma_chunk / mfma_chunks: its units)."""
     l = lib()
     ptrs, counts, keep = _channel_arrays(packets)
     h = C.c_void_p()
@@ -384,9 +386,14 @@ def build_tiles(packets, impl, ob_bank, vb_bank, num_rows, num_cols, num_row_par
         wg_first = np.zeros(nwg.value + 1, dtype=np.uint32)
         order = np.zeros(max(nblocks.value, 1), dtype=np.uint32)
         l.hs_tiles_copy(h, image.ctypes.data, blocks.ctypes.data, units.ctypes.data, wg_first.ctypes.data, order.ctypes.data)
+        mbytes, chunk, chunks = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        l.hs_tiles_mfma(h, None, 0, C.byref(mbytes), C.byref(chunk), C.byref(chunks))
+        mfma = np.zeros(max(mbytes.value, 1), dtype=np.uint8)
+        if mbytes.value:
+            l.hs_tiles_mfma(h, mfma.ctypes.data, mfma.size, None, None, None)
         return dict(image=image[:nbytes.value], blocks=blocks[:nblocks.value], units=units[:nunits.value], wg_first=wg_first,
                     block_order=order[:nblocks.value], num_workgroups=nwg.value, max_block_rows=maxrows.value, nnz=nnz.value,
                     elements=elems.value, col_slices=slices.value, ring_buffers=ring.value,
-                    format=STREAM_FORMATS[fmt.value])
+                    format=STREAM_FORMATS[fmt.value], mfma=mfma[:mbytes.value], mfma_chunk=chunk.value, mfma_chunks=chunks.value)
     finally:
         l.hs_tiles_free(h)

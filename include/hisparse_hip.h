@@ -175,7 +175,7 @@ int hs_push_result(hs_context* ctx, void* const* dst, uint32_t n_dst, uint32_t n
  * The library's configuration surface.  key: the name of a tuning switch, case-insensitive, with or without the "HISPARSE_" prefix of its
  * environment spelling -- plan-time keys (take effect at the NEXT hs_load_matrix / hs_load_matrix_csr of this context): stream_format
  * (pairs|delta|owner|owner24|sweep|bitmap), col_slices, max_rows, cross_partitions (0: row blocks end at the reference's row-partition borders), spmm_vectors (4: plan the image for the four-column SpMM kernel, see hs_spmm), row_runs, delta_deal (wave: the dealing of DELTA runs of rounds 1-4), pow2_slices (1: column-slice counts 1, 2, 4, 8 only for matrices of more than sixteen sub-tiles, the rule of rounds 1-4), aux_bits, xcd_affinity, retile (host), bitmap_skew, bitmap_x_lds,
- * bitmap_build, walk_lanes, no_mfma_image, mfma_chunk, light (0|1: the small-matrix kernel), sweep (0|1: the
+ * bitmap_build, walk_lanes, no_mfma_image, mfma_chunk (1 ... 65536 groups per wavefront unit of the matrix engine's image; a unit of all the groups of a row or more is the whole row; anything else is HS_ERR_BAD_ARG here, or from the load when it comes from the environment), light (0|1: the small-matrix kernel), sweep (0|1: the
  * column-ordered format of very sparse matrices), plan_debug; call-time keys: spmm_fused, spmm_mfma,
  * spmspv (sparse|auto|dense), spmspv_crossover, iterate_graph, batch_graph (hs_run_batch); carry_combine (0|1, plan-time: see hs_run), stream_resident (0|1, plan-time: SWEEP and PAIRS / DELTA images streamed without the non-temporal hint; default: SWEEP images up to 256 MiB, the Infinity Cache; PAIRS / DELTA images up to 256 MiB whose blocks walk several units, or up to 32 MiB: hs_stats.stream_resident says what the plan took).  autotune (0|1, plan-time, round 6: the load builds the planner's own image AND every other element format the matrix can take, times a few SpMVs of each on a zero vector and keeps the fastest -- a handful of extra loads of tens of milliseconds each, for callers that run one matrix thousands of times; a forced stream_format switches it off; hs_get_stats says what was kept), plan_census (0: plan from the rows' non-zero counts alone, as rounds 1-5 did), value_map (0|1, plan-time: hs_load_matrix_csr keeps the value map of hs_update_values).  value NULL or "" clears the option.  An unknown key is HS_ERR_BAD_ARG.
  * Options set here win over the environment variable of the same name, which stays as the fallback for tools and tests.  None of them
@@ -354,6 +354,10 @@ int hs_tiles_info(const hs_tiles* t, uint64_t* image_bytes, uint32_t* num_blocks
 /* image: image_bytes; blocks: num_blocks x 320 B; units: num_units x 64 B (layouts: hisparse_amd/csrc/stream_tiles.h);
  * wg_first: num_workgroups + 1; block_order: num_blocks */
 int hs_tiles_copy(const hs_tiles* t, void* image, void* blocks, void* units, uint32_t* wg_first, uint32_t* block_order);
+/* The second image of a float BITMAP matrix as the host builder lays it out (what hs_debug_read_mfma_image reads back from a context):
+ * *bytes = its size (0: none), *chunk = groups per wavefront unit, *chunks = units per row tile; copied out when `words` is not NULL
+ * (capacity >= *bytes).  Any pointer may be NULL. */
+int hs_tiles_mfma(const hs_tiles* t, void* words, uint64_t capacity, uint64_t* bytes, uint32_t* chunk, uint32_t* chunks);
 void hs_tiles_free(hs_tiles* t);
 const char* hs_tiles_last_error(void);
 

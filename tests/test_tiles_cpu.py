@@ -455,6 +455,20 @@ def test_empty_environment_switches_count_as_unset(monkeypatch):
     assert got["format"] == want["format"] and np.array_equal(got["image"], want["image"]) and got["blocks"].tobytes() == want["blocks"].tobytes()
 
 
+def test_plan_debug_prints_the_passes_and_changes_nothing(monkeypatch, capfd):
+    """HISPARSE_PLAN_DEBUG: the wall time of the builder's passes on stderr; the same plan, image and tables"""
+    m = cases.random_csr(3000, 700, 0.02, 5, 0)
+    _, cp = cases.formatted(m, 0, 16, 8, True)
+    monkeypatch.delenv("HISPARSE_PLAN_DEBUG", raising=False)
+    quiet = build(cp, 0, 7)
+    capfd.readouterr()
+    monkeypatch.setenv("HISPARSE_PLAN_DEBUG", "1")
+    loud = build(cp, 0, 7)
+    assert "re-tile" in capfd.readouterr().err
+    assert loud["format"] == quiet["format"] and np.array_equal(loud["image"], quiet["image"])
+    assert loud["blocks"].tobytes() == quiet["blocks"].tobytes() and loud["units"].tobytes() == quiet["units"].tobytes()
+
+
 def test_worker_pool(tmp_path):
     """parallel_for of the load-time builders runs on parked worker threads (tiles_common.h: WorkerPool): tests/cpp/test_worker_pool.cpp."""
     import subprocess

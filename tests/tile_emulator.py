@@ -307,3 +307,48 @@ def run(tiles, impl, x_words, num_rows, row_part_filter=-1, y_init=None, rows_pe
     elif filtered:
         y[part_lo:part_hi] = out[part_lo:part_hi]
     return y
+
+
+MFMA_TILE_ROWS = 16          # stream_tiles.h: kMfmaTileRows
+
+
+def run_mfma(words, chunk, chunks, num_rows, num_cols, x_words):
+    """spmm_mfma_kernel + spmm_finish_kernel over the second image of a float BITMAP matrix (stream_tiles.h: MfmaImage; `words`: its bytes,
+    from build_tiles or read_mfma_image), unit for unit: a wavefront unit is a tile of 16 rows x `chunk` 64-column groups, `chunks` units
+    per tile (a multiple of 4; the last ones may hold no group).  Masks [tile][group][16 rows] of 64 bits, the units' first value
+    [tile][chunks], then the values in (group, column, row) order.  x_words: (k, >= num_cols) packed vectors; returns (k, num_rows)
+    packed fp32: per row the fp32 products of its stored elements, summed in double."""
+    x_words = np.atleast_2d(np.asarray(x_words, dtype=np.uint32))
+    groups, tiles = (num_cols + 63) // 64, (num_rows + MFMA_TILE_ROWS - 1) // MFMA_TILE_ROWS
+    assert chunk >= 1 and chunks == ((groups + chunk - 1) // chunk + 3) // 4 * 4
+    words = np.ascontiguousarray(words).view(np.uint32)
+    offsets_word = tiles * groups * MFMA_TILE_ROWS * 2
+    values_word = offsets_word + tiles * chunks
+    masks = words[:offsets_word].view(np.uint64).reshape(tiles, groups, MFMA_TILE_ROWS)
+    unit_base = words[offsets_word: values_word].reshape(tiles, chunks)
+    values = words[values_word:]
+    xf = np.zeros((x_words.shape[0], groups * 64), dtype=np.float32)      # interleave_x16_kernel zero-fills up to whole groups
+    xf[:, :num_cols] = x_words[:, :num_cols].view(np.float32)
+    ys = np.zeros((x_words.shape[0], tiles * MFMA_TILE_ROWS), dtype=np.float64)
+    expect = 0                                                             # the units' values lie back to back, tile by tile
+    for t in range(tiles):
+        for c in range(chunks):
+            base = int(unit_base[t, c])
+            assert base == expect, (t, c, base, expect)
+            g0 = min(groups, c * chunk)
+            g1 = min(groups, g0 + chunk)
+            for g in range(g0, g1):
+                bits = np.unpackbits(masks[t, g].view(np.uint8).reshape(MFMA_TILE_ROWS, 8), axis=1, bitorder="little").astype(bool)    # [row, column]
+                col, row = np.nonzero(bits.T)                              # column-major: step 4 s + k, then the rows of the tile
+                n = col.size
+                assert (64 * g + col < num_cols).all() and (MFMA_TILE_ROWS * t + row < num_rows).all()
+                v = values[base: base + n].view(np.float32)
+                with np.errstate(all="ignore"):
+                    p = (v[None, :] * xf[:, 64 * g + col]).astype(np.float32).astype(np.float64)
+                for j in range(ys.shape[0]):
+                    np.add.at(ys[j], MFMA_TILE_ROWS * t + row, p[j])
+                base += n
+            expect = base
+    assert values_word + expect + 64 == words.size                         # every value belongs to a unit; 64 words of slack behind them
+    with np.errstate(all="ignore"):
+        return ys[:, :num_rows].astype(np.float32).view(np.uint32)
