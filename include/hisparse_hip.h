@@ -298,7 +298,9 @@ int hs_load_matrix_csr_transposed(hs_context* ctx, uint32_t num_rows, uint32_t n
  * 65535 columns); or it is 16 GiB or larger.
  * The CSC matrix of hs_spmspv is NOT updated: under spmspv = auto, "the same matrix both ways" stays the caller's contract -- load the CSC
  * matrix again with the new values, or leave the dense dispatch off.
- * (The product that MAKES such values in this order, dW[e] = sum_j U_j[row(e)] V_j[col(e)], is an object of its own: hisparse_pattern.h.) */
+ * (The product that MAKES such values in this order, dW[e] = sum_j U_j[row(e)] V_j[col(e)], is an object of its own: hisparse_pattern.h.
+ * Callers whose values change on EVERY step and whose dense operands are row-major node features, [index][feature], need neither this
+ * call nor a context for the products with those values: hisparse_wide.h reads the values from a device array in CSR order on each call.) */
 int hs_update_values(hs_context* ctx, const float* values, uint64_t nnz);
 int hs_update_values_device(hs_context* ctx, const float* values_dev, uint64_t nnz);
 
