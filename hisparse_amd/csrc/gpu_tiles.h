@@ -61,8 +61,14 @@ class GpuTiler {
     // (detail::balanced_owner_shares; max_span = kOwnerShareRows for OWNER24, 0xffffffff otherwise)
     bool owner_shares(std::vector<detail::UnitPlan>& plans, uint32_t max_span);
     // The image (image_bytes + slack, zero-filled first).  format: the final StreamFormat; block_of_unit / blocks: pre-reorder indices.
+    // value_bits == 24 (DELTA only): the packed 640-byte record with this value_shift; the `outliers` value words that do not fit go out as
+    // (unit, {local row, absolute column, value word}) in the order of the sorted elements -- units, then positions -- and are ALSO copied into the image's
+    // tail (the last ceil16(outliers x 12) bytes of image_bytes), which is where the host builder puts them.
     bool emit(StreamFormat format, uint64_t image_bytes, uint64_t slack_bytes, const std::vector<detail::UnitPlan>& plans,
-              const std::vector<uint32_t>& block_of_unit, const std::vector<Block>& blocks, bool is_float);
+              const std::vector<uint32_t>& block_of_unit, const std::vector<Block>& blocks, bool is_float, uint32_t value_bits, uint32_t value_shift,
+              uint64_t outliers, const std::vector<Unit>& units, std::vector<uint32_t>& outlier_unit, std::vector<Outlier>& outlier_entry);
+    // DELTA, fixed point: for every shift 0 .. kMaxValueShift, the sorted value words that do not fit a 24-bit field (stream_tiles.h: value_fits24)
+    bool count_value_misfits(uint64_t (&misfits)[kMaxValueShift + 1]);
     // ---- BITMAP (bitmap_tiles.cpp plans; masks, values, run heads and the matrix-engine image are made here) -------------------------
     // non-zeros per (row, column slice of groups): cnt[row * slices + k]; slice k = groups [k GR / slices, (k + 1) GR / slices)
     bool bitmap_slice_counts(uint32_t slices, uint32_t groups_per_row, std::vector<uint32_t>& cnt);

@@ -503,6 +503,71 @@ __global__ __launch_bounds__(256) void emit_delta_kernel(const DevicePlan* __res
     }
 }
 
+// DELTA with 24-bit value fields (stream_tiles.h: kRecordBytes24): one thread writes BOTH slots of a lane's record -- the lane's 8 bytes hold
+// field A, field B and gap A, so the two slots share a word.  An element whose value word does not fit carries field 0 and is appended, with
+// its index among the sorted elements, to a list the host puts into order (the order of the sorted elements: what the host builder emits).
+struct DeviceOutlier { uint64_t element; uint32_t pos, value; };
+__global__ __launch_bounds__(256) void emit_delta24_kernel(const DevicePlan* __restrict__ plans, const uint64_t* __restrict__ keys,
+                                                          const uint32_t* __restrict__ vals, const uint64_t* __restrict__ bridges,
+                                                          uint8_t* __restrict__ image, uint32_t shift, DeviceOutlier* __restrict__ outliers,
+                                                          uint32_t* __restrict__ outlier_count, uint32_t outlier_capacity) {
+    const DevicePlan& p = plans[blockIdx.x];
+    if (!p.n) return;
+    const uint32_t scratch_pos = p.nrows * kSubTileCols;      // local row nrows = the spare accumulator
+    const uint32_t first_pos = uint32_t(keys[p.start] & kPosMask);
+    for (uint32_t w = 0; w < kConsumerWaves; ++w) {
+        const uint32_t run = p.run_len[w];
+        if (!run) continue;
+        uint8_t* rec = image + p.wave_offset[w] + uint64_t(p.start_step[w]) * kRecordBytes24;
+        const uint32_t records = (run + 2) / 2;                                                  // head + run, in whole two-slot records
+        for (uint32_t idx = threadIdx.x; idx < records * kWaveLanes; idx += blockDim.x) {
+            const uint32_t r = idx / kWaveLanes, l = idx % kWaveLanes;
+            const uint64_t s0 = p.first_slot[w] + uint64_t(l) * p.lane_stride[w];
+            uint32_t field[2] = {0, 0}, gap[2] = {0, 0};                                         // fixed point: padding and dead slots are (gap 0, value 0)
+            for (uint32_t h = 0; h < 2; ++h) {
+                const uint32_t j = 2 * r + h;                                                    // j = 0: the head slot
+                if (j == 0) {
+                    uint32_t head = scratch_pos;
+                    if (s0 < p.slots) head = s0 == 0 ? first_pos : delta_slot(p, keys, vals, bridges, s0 - 1).after;
+                    field[0] = head & 0xffffffu;                                                 // the head's position: field A | gap A << 24
+                    gap[0] = head >> 24;
+                    continue;
+                }
+                const uint64_t si = s0 + (j - 1);
+                if (j > run || si >= p.slots) continue;
+                const Slot s = delta_slot(p, keys, vals, bridges, si);
+                gap[h] = s.gap;
+                if (value_fits24(s.val, shift)) {
+                    field[h] = s.val >> shift;
+                } else {                                                                         // (bridges carry value 0, which fits)
+                    const uint32_t k = atomicAdd(outlier_count, 1u);
+                    if (k < outlier_capacity) outliers[k] = DeviceOutlier{s.e, s.after, s.val};
+                }
+            }
+            uint8_t* at = rec + uint64_t(r) * kRecordBytes24;
+            reinterpret_cast<uint64_t*>(at)[l] = uint64_t(field[0]) | uint64_t(field[1]) << 24 | uint64_t(gap[0]) << 48;
+            reinterpret_cast<uint16_t*>(at + kWaveLanes * 8)[l] = uint16_t(gap[1]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void value_misfits_kernel(const uint32_t* __restrict__ vals, uint64_t n, unsigned long long* __restrict__ misfits) {
+    __shared__ uint32_t local[kMaxValueShift + 1];
+    if (threadIdx.x <= kMaxValueShift) local[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t mine[kMaxValueShift + 1] = {0};
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint32_t v = vals[i];
+#pragma unroll
+        for (uint32_t sh = 0; sh <= kMaxValueShift; ++sh) mine[sh] += !value_fits24(v, sh);
+    }
+#pragma unroll
+    for (uint32_t sh = 0; sh <= kMaxValueShift; ++sh)
+        if (mine[sh]) atomicAdd(&local[sh], mine[sh]);
+    __syncthreads();
+    if (threadIdx.x <= kMaxValueShift && local[threadIdx.x]) atomicAdd(&misfits[threadIdx.x], static_cast<unsigned long long>(local[threadIdx.x]));
+}
+
 // ---- BITMAP (bitmap_tiles.cpp; kernel: spmv_bitmap.hip) -------------------------------------------------------------------------
 // The planning (row ranges, slices, block layout, wavefront runs) stays on the host; these kernels do what touches every non-zero:
 // count per (row, slice), set the bit, prefix-count the masks per row, place the value, and the same for the matrix-engine image.
@@ -1061,8 +1126,31 @@ bool GpuTiler::owner_shares(std::vector<UnitPlan>& plans, uint32_t max_span) {
     return ok;
 }
 
+bool GpuTiler::count_value_misfits(uint64_t (&misfits)[kMaxValueShift + 1]) {
+    for (uint64_t& m : misfits) m = 0;
+    if (!total_) return true;
+    DeviceBuffer<unsigned long long> d_misfits;
+    unsigned long long host[kMaxValueShift + 1] = {0};
+    bool ok = check(d_misfits.alloc_count(kMaxValueShift + 1, 16), "hipMalloc") && check(hipMemsetAsync(d_misfits.get(), 0, sizeof(host), stream_), "hipMemset");
+    if (ok) {
+        const uint32_t grid = uint32_t(std::min<uint64_t>((total_ + 255) / 256, 4096));
+        hipLaunchKernelGGL(value_misfits_kernel, dim3(grid), dim3(256), 0, stream_, d_vals_.get(), total_, d_misfits.get());
+        ok = check(hipGetLastError(), "value_misfits_kernel") && check(hipMemcpyAsync(host, d_misfits.get(), sizeof(host), hipMemcpyDeviceToHost, stream_), "read misfits") &&
+             check(hipStreamSynchronize(stream_), "value misfits");
+    }
+    for (uint32_t sh = 0; ok && sh <= kMaxValueShift; ++sh) misfits[sh] = host[sh];
+    return ok;
+}
+
 bool GpuTiler::emit(StreamFormat format, uint64_t image_bytes, uint64_t slack_bytes, const std::vector<UnitPlan>& plans,
-                    const std::vector<uint32_t>& block_of_unit, const std::vector<Block>& blocks, bool is_float) {
+                    const std::vector<uint32_t>& block_of_unit, const std::vector<Block>& blocks, bool is_float, uint32_t value_bits, uint32_t value_shift,
+                    uint64_t outliers, const std::vector<Unit>& units, std::vector<uint32_t>& outlier_unit, std::vector<Outlier>& outlier_entry) {
+    outlier_unit.clear();
+    outlier_entry.clear();
+    const bool packed = format == kFormatDelta && value_bits == 24;
+    if (packed && (is_float || d_src_ || outliers > 0xffffffffull)) return fail("gpu re-tile: the packed DELTA record is fixed-point only and keeps no value map");
+    DeviceBuffer<DeviceOutlier> d_outliers;
+    DeviceBuffer<uint32_t> d_outlier_count;
     std::vector<DevicePlan> dp;
     make_device_plans(plans, block_of_unit, blocks, dp);
     DeviceBuffer<DevicePlan> d_plans;
@@ -1092,6 +1180,14 @@ bool GpuTiler::emit(StreamFormat format, uint64_t image_bytes, uint64_t slack_by
                 hipLaunchKernelGGL((m ? emit_owner_kernel<true, true> : emit_owner_kernel<true, false>), grid, block, 0, stream_, p, keys, vals, image, src, map);
                 break;
             case kFormatDelta:
+                if (packed) {
+                    ok = check(d_outliers.alloc_count(std::max<uint64_t>(outliers, 1), 16), "hipMalloc(outliers)") && check(d_outlier_count.alloc_count(1, 16), "hipMalloc") &&
+                         check(hipMemsetAsync(d_outlier_count.get(), 0, 4, stream_), "hipMemset");
+                    if (ok)
+                        hipLaunchKernelGGL(emit_delta24_kernel, grid, block, 0, stream_, p, keys, vals, d_bridges_.get(), image, value_shift, d_outliers.get(),
+                                           d_outlier_count.get(), uint32_t(outliers));
+                    break;
+                }
                 hipLaunchKernelGGL(m ? emit_delta_kernel<true> : emit_delta_kernel<false>, grid, block, 0, stream_, p, keys, vals, d_bridges_.get(), image,
                                    is_float ? kBridgeGap : 0u, src, map);
                 break;
@@ -1100,6 +1196,26 @@ bool GpuTiler::emit(StreamFormat format, uint64_t image_bytes, uint64_t slack_by
         ok = ok && check(hipGetLastError(), "emit kernel");
     }
     ok = ok && check(hipStreamSynchronize(stream_), "emit");
+    if (ok && packed && !plans.empty()) {
+        // the outliers: into the order of the sorted elements, then into the image's tail and out to the caller (who sets the blocks' list fields)
+        uint32_t found = 0;
+        ok = check(hipMemcpy(&found, d_outlier_count.get(), 4, hipMemcpyDeviceToHost), "read outlier count");
+        if (ok && found != outliers) ok = fail("gpu re-tile: the emit pass found another number of outliers than the counting pass");
+        std::vector<DeviceOutlier> list(found);
+        if (ok && found) ok = check(hipMemcpy(list.data(), d_outliers.get(), size_t(found) * sizeof(DeviceOutlier), hipMemcpyDeviceToHost), "read outliers");
+        if (ok && found) {
+            std::sort(list.begin(), list.end(), [](const DeviceOutlier& a, const DeviceOutlier& b) { return a.element < b.element; });
+            for (const DeviceOutlier& o : list) {
+                // the unit of sorted element e: the last one that starts at or before it (units without elements start where the next one does)
+                size_t lo = 0, hi = plans.size();
+                while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if (plans[mid].scratch <= o.element) lo = mid; else hi = mid; }
+                outlier_unit.push_back(uint32_t(lo));
+                outlier_entry.push_back(Outlier{o.pos / kSubTileCols, units[lo].col0 + o.pos % kSubTileCols, o.value});
+            }
+            const uint64_t tail = (uint64_t(found) * sizeof(Outlier) + 15u) & ~uint64_t(15);
+            ok = check(hipMemcpy(d_image_.get() + image_bytes - tail, outlier_entry.data(), size_t(found) * sizeof(Outlier), hipMemcpyHostToDevice), "write outliers");
+        }
+    }
     // keys, values, bridges and sources go back now; a failed emit keeps image and map until the tiler goes (bitmap_emit and sweep_emit give theirs back at once)
     d_keys_.reset();
     d_vals_.reset();

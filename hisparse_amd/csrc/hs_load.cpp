@@ -52,6 +52,7 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
     if (csr_in) {
         csr_view = *csr_in;
         csr_view.value_map = map_on && want_map;
+        csr_view.plain_values = map_on;
         csr = &csr_view;
     }
 
@@ -151,9 +152,12 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
     const uint64_t image_bytes = image_on_device ? tiles.image_bytes : uint64_t(tiles.image.size());
     const char* resident_opt = ctx_option(ctx, "HISPARSE_STREAM_RESIDENT");
     m.launch.stream_resident = resident_opt ? std::atoi(resident_opt) != 0
-                                     : hisparse::dev::plan_stream_resident(tiles.format, tiles.light, image_bytes, tiles.units.size(), tiles.blocks.size());
+                                     : hisparse::dev::plan_stream_resident(tiles.format, tiles.light, image_bytes, tiles.units.size(), tiles.blocks.size(), tiles.value_bits);
     const char* carry_opt = ctx_option(ctx, "HISPARSE_CARRY_COMBINE");
-    const bool carries = tiles.col_slices > 1 && (carry_opt ? std::atoi(carry_opt) != 0 : hisparse::dev::plan_carries(tiles.format, image_bytes));
+    // (a packed DELTA image is judged by the size of its plain form here too: packing changes the bytes of a step, not which of the two regimes it is in)
+    const uint64_t carry_bytes = tiles.format == hisparse::dev::kFormatDelta && tiles.value_bits == 24
+                                     ? image_bytes / hisparse::dev::kRecordBytes24 * hisparse::dev::kRecordBytes : image_bytes;
+    const bool carries = tiles.col_slices > 1 && (carry_opt ? std::atoi(carry_opt) != 0 : hisparse::dev::plan_carries(tiles.format, carry_bytes));
     HS_HIP(ctx, ctx->carry.reset(ctx->is_float(), num_rows, num_cols, tiles.col_slices, carries));
     if (mfma_on_device || (tiles.mfma.words_bytes != 0 && !tiles.mfma.words.empty())) {      // float BITMAP matrix: the second image for the SpMM on the matrix engine + its scratch
         // OPTIONAL: SpMV works without it.  If the image or its scratch cannot be had (out of memory), the matrix loads without a second
@@ -206,6 +210,7 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
     a.part_heads = m.part_heads.get();
     a.ring_buffers = tiles.ring_buffers;
     a.format = tiles.format;
+    a.value_bits = tiles.value_bits;
     a.num_cols = num_cols;
     a.num_workgroups = tiles.num_workgroups;
     a.lds_bytes = lds_bytes;
@@ -231,6 +236,7 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
     s.load_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     s.retiled_on_gpu = image_on_device;
     s.light_kernel = tiles.light ? 1u : 0u;
+    s.value_bits = tiles.value_bits;
     s.stream_resident = a.stream_resident && hisparse::dev::stream_policy_applies(tiles.format, tiles.light) ? 1u : 0u;
     return HS_OK;
 }

@@ -21,6 +21,7 @@ struct SpmvLaunch {
     int32_t row_part_filter;      // -1: every row partition
     uint32_t ring_buffers;        // x sub-tile buffers in the LDS ring (2..4)
     uint32_t format;              // StreamFormat of `image` (stream_tiles.h): PAIRS chunks, DELTA records or BITMAP rows
+    uint32_t value_bits = 0;      // DELTA images: 24 = packed 640-byte records (StreamTiles::value_bits), else the plain 768-byte ones
     uint32_t num_cols;            // length of x in words (BITMAP: the x reads of a row's last group are range-checked against it)
     uint32_t num_workgroups;
     uint32_t lds_bytes;

@@ -125,11 +125,14 @@ constexpr int kMaxDepth = 16;
 constexpr int kOwner24Depth = 3;     // OWNER24: records in flight per wavefront (5.25 KiB)
 
 // kRing & 3: 0 = PAIRS / OWNER with 32-bit position words, 1 = DELTA, 2 = PAIRS / OWNER with 24-bit position words, 3 = OWNER24 records;
-// kRing & 4: the image stays in the Infinity Cache (stream loads with HS_ROWBLOCK_RESIDENT_POLICY instead of `nt`)
+// kRing & 4: the image stays in the Infinity Cache (stream loads with HS_ROWBLOCK_RESIDENT_POLICY instead of `nt`);
+// kRing & 8 (with kRing & 3 == 0): DELTA with 24-bit value fields, 640-byte records (stream_tiles.h: kRecordBytes24) -- ring format 4
+constexpr int ring_format(int kRing) { return (kRing & 8) ? 4 : (kRing & 3); }
+constexpr bool ring_is_delta(int kRing) { return ring_format(kRing) == 1 || ring_format(kRing) == 4; }
 template <int kFmt, bool kRes>
 struct RingT;
 template <int kRing>
-using Ring = RingT<(kRing & 3), (kRing & 4) != 0>;
+using Ring = RingT<ring_format(kRing), (kRing & 4) != 0>;
 template <bool kRes>
 struct RingT<0, kRes> {   // PAIRS: one dwordx2 per lane and step
     static constexpr uint32_t kLaneBytes = 8;
@@ -171,6 +174,30 @@ struct RingT<1, kRes> {    // DELTA: a record = two slots per lane: {value A, va
     static __device__ __forceinline__ void take_record(uint32_t& value_a, uint32_t& value_b, uint32_t& gaps) {
         asm volatile("s_waitcnt vmcnt(%6)\n\tv_accvgpr_read_b32 %0, a[%3]\n\tv_accvgpr_read_b32 %1, a[%4]\n\tv_accvgpr_read_b32 %2, a[%5]"
                      : "=v"(value_a), "=v"(value_b), "=v"(gaps) : "n"(2 * K), "n"(2 * K + 1), "n"(K + kMaxDepth), "n"(2 * (kDepth - 1)) : "memory");
+    }
+};
+template <bool kRes>
+struct RingT<4, kRes> {    // DELTA, 24-bit value fields: a record = two slots per lane: {field A, field B, gap A} as one dwordx2, gap B as one 16-bit load
+    static constexpr uint32_t kLaneBytes = 8;
+    template <int K>
+    static __device__ __forceinline__ void issue(const uint8_t* base, uint32_t byte_off, uint32_t lane_off) {
+        static_assert(2 * K + 1 < kMaxDepth && K + kMaxDepth < 2 * kMaxDepth, "dwordx2 in a0..a15, gap B in a16..a23: ring depth <= 8");
+#define HS_ISSUE(P)                                                                                                                                         \
+    asm volatile("s_nop 4\n\tglobal_load_dwordx2 a[%0:%1], %3, %5 " P "\n\tglobal_load_ushort a[%2], %4, %5 offset:512 " P ::"n"(2 * K), "n"(2 * K + 1),    \
+                 "n"(K + kMaxDepth), "v"(byte_off + lane_off), "v"(byte_off + lane_off / 4), "s"(base)                                                     \
+                 : "memory", HS_RING_AGPRS)
+        HS_BY_POLICY(kRes, HS_ISSUE);
+#undef HS_ISSUE
+    }
+    // the two 24-bit value fields (not yet shifted) and the gaps, A in the low half, B in the high half -- the shape RingT<1>::take_record hands out
+    template <int K, int kDepth>
+    static __device__ __forceinline__ void take_record(uint32_t& field_a, uint32_t& field_b, uint32_t& gaps) {
+        uint32_t lo, hi, gap_b;
+        asm volatile("s_waitcnt vmcnt(%6)\n\tv_accvgpr_read_b32 %0, a[%3]\n\tv_accvgpr_read_b32 %1, a[%4]\n\tv_accvgpr_read_b32 %2, a[%5]"
+                     : "=v"(lo), "=v"(hi), "=v"(gap_b) : "n"(2 * K), "n"(2 * K + 1), "n"(K + kMaxDepth), "n"(2 * (kDepth - 1)) : "memory");
+        field_a = lo & 0xffffffu;
+        field_b = __builtin_amdgcn_alignbit(hi, lo, 24) & 0xffffffu;
+        gaps = (hi >> 16) | (gap_b << 16);      // (the 16-bit load zero-extends)
     }
 };
 template <bool kRes>
@@ -257,6 +284,7 @@ struct Consumer {
     uint32_t next_end = 0;     // end_step of unit u + 1, requested one unit ahead (a scalar load whose latency is off the unit boundary)
     const uint32_t* xb;
     uint32_t pos = 0;          // DELTA: this lane's position in the current sub-tile
+    uint32_t value_shift = 0;  // DELTA with 24-bit value fields: value word = field << value_shift (Block::value_shift, wave-uniform)
     bool head = true;          // DELTA: the next record of this wavefront is a head record
     uint32_t run_row = kNoRow; // PAIRS dense rows: row whose products are being summed in registers ...
     typename Rows<kFloat>::sum_t run_sum = 0;   // ... and this lane's share of that sum (float: in double, like every sum of products here)
@@ -291,8 +319,8 @@ __device__ __forceinline__ void timeline_stamp(uint32_t k, uint32_t wave, uint32
 template <bool kFloat, int kRing, int kAblate, int kDepth, bool kDense, int K>
 __device__ __forceinline__ bool consume_step(Consumer<kFloat>& c) {
     using R = Rows<kFloat>;
-    constexpr bool kDelta = (kRing & 3) == 1, k24 = (kRing & 3) == 2;      // (kRing & 4: the cache policy of the stream loads, Ring<>)
-    constexpr uint32_t kStride = kDelta ? kRecordBytes : k24 ? kWaveStrideBytes24 : kWaveStrideBytes;
+    constexpr bool kDelta = ring_is_delta(kRing), kPacked = ring_format(kRing) == 4, k24 = ring_format(kRing) == 2;      // (kRing & 4: the cache policy of the stream loads, Ring<>)
+    constexpr uint32_t kStride = kPacked ? kRecordBytes24 : kDelta ? kRecordBytes : k24 ? kWaveStrideBytes24 : kWaveStrideBytes;
     constexpr uint32_t kColMask = k24 ? kSubTileCols - 1u : 0xffffu, kRowShift = k24 ? kOwnerColBits : 16u;
     const uint32_t s = c.base + K;
     while (s == c.end) {               // this wavefront finished sub-tile u (possibly with no work in it)
@@ -350,13 +378,14 @@ __device__ __forceinline__ bool consume_step(Consumer<kFloat>& c) {
                 R::add(c.ys, row, prod);
             }
         };
+        // (24-bit value fields: the head's position is field A | gap A << 24; every other field is shifted into its value word)
         if (c.head) {                  // wave-uniform: slot A is the head
-            c.pos = value_a;
+            c.pos = kPacked ? (value_a | (gaps << 24)) : value_a;
             c.head = false;
         } else {
-            slot(value_a, gaps & 0xffffu);
+            slot(kPacked ? value_a << c.value_shift : value_a, gaps & 0xffffu);
         }
-        slot(value_b, gaps >> 16);
+        slot(kPacked ? value_b << c.value_shift : value_b, gaps >> 16);
     } else {
         Ring<kRing>::template take<K, kDepth>(mat, aux);
         const uint32_t xv = (kAblate & 2) ? aux : c.xb[aux & kColMask];
@@ -687,8 +716,8 @@ __device__ __forceinline__ void consumer_begin(Consumer<kFloat>& c, const uint8_
                                                uint32_t lane, const uint32_t* xs, uint32_t ring, typename Rows<kFloat>::acc_t* ys, uint32_t nrows,
                                                uint32_t total, uint32_t first_end) {
     static_assert(kDepth <= kMaxDepth, "the ring lives in a0..a31");
-    constexpr bool kDelta = (kRing & 3) == 1, k24 = (kRing & 3) == 2;      // (kRing & 4: the cache policy of the stream loads, Ring<>)
-    constexpr uint32_t kStride = kDelta ? kRecordBytes : kOwner ? kChunkBytes : k24 ? kWaveStrideBytes24 : kWaveStrideBytes;
+    constexpr bool kDelta = ring_is_delta(kRing), kPacked = ring_format(kRing) == 4, k24 = ring_format(kRing) == 2;      // (kRing & 4: the cache policy of the stream loads, Ring<>)
+    constexpr uint32_t kStride = kPacked ? kRecordBytes24 : kDelta ? kRecordBytes : kOwner ? kChunkBytes : k24 ? kWaveStrideBytes24 : kWaveStrideBytes;
     c.stream = scalar_pointer(stream);
     c.unit = unit; c.U = U; c.wave = wave; c.lane = lane; c.ring = ring; c.nrows = nrows;
     c.lane_off = lane * Ring<kRing>::kLaneBytes;
@@ -734,11 +763,12 @@ __device__ __forceinline__ void consumer_run(Consumer<kFloat>& c) {
 // bit 5 = no result store, bit 6 = ignore unit boundaries.  Any non-zero value gives wrong results.
 // kRing: 1 = the image is in the DELTA stream format (stream_tiles.h), 0 = PAIRS / OWNER chunks with 32-bit position words, 2 = with 24-bit ones.
 // kOwner: the image is in the OWNER format (float only): 4-byte float accumulators, nrows + 14 of them.
+// (the body of the two kernels below: spmv_rowblock_kernel and -- DELTA images with 24-bit value fields -- spmv_rowblock_kernel_delta24)
 template <bool kFloat, int kRing, int kAblate, int kDepth, bool kOwner = false>
-__global__ __launch_bounds__(kThreads) void spmv_rowblock_kernel(const uint8_t* __restrict__ image, const Block* __restrict__ blocks,
-                                                                  const Unit* __restrict__ units, const uint32_t* __restrict__ x,
-                                                                  uint32_t* __restrict__ out, int32_t row_part_filter, uint32_t ring,
-                                                                  uint32_t x_base, const uint32_t* __restrict__ part_heads, CarriedCombine carry) {
+__device__ __forceinline__ void rowblock_workgroup(const uint8_t* __restrict__ image, const Block* __restrict__ blocks,
+                                                   const Unit* __restrict__ units, const uint32_t* __restrict__ x,
+                                                   uint32_t* __restrict__ out, int32_t row_part_filter, uint32_t ring,
+                                                   uint32_t x_base, const uint32_t* __restrict__ part_heads, const CarriedCombine& carry) {
     using acc_t = typename Rows<kFloat>::acc_t;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     acc_t* ys = reinterpret_cast<acc_t*>(lds);                    // [nrows + 1] at LDS address 0: row addresses need no base add
@@ -780,6 +810,7 @@ __global__ __launch_bounds__(kThreads) void spmv_rowblock_kernel(const uint8_t* 
             else
                 consumer_begin<kFloat, kRing, kDepth, kOwner>(c, image + blk->wave_offset[wave], unit, U, wave, lane, xs, ring, ys, nrows, blk->total_steps[wave],
                                                                blk->first_end[wave]);
+            if constexpr (ring_format(kRing) == 4) c.value_shift = blk->value_shift;
         }
         // y of the PREVIOUS step (spmv_device.h: CarriedCombine), once per launch, HERE: the consumers' first stream loads (and the block
         // descriptor behind them) are already travelling, so the round trip of the partial rows overlaps theirs instead of preceding it
@@ -881,6 +912,19 @@ __global__ __launch_bounds__(kThreads) void spmv_rowblock_kernel(const uint8_t* 
             if (!next) break;
             continue;
         }
+        if constexpr (ring_format(kRing) == 4) {
+            // DELTA with 24-bit value fields: the block's OUTLIERS -- value words that did not fit the field; their slots in the stream carry 0 -- are
+            // added here, after the last unit and in front of the flush: {local row, absolute column, value word} each, x read from global memory.
+            // At most one per 4096 element slots of the image (stream_tiles.h), so the walk is almost always empty and never more than a step's worth.
+            const uint32_t n_out = blk->outlier_count;
+            if (!loader && n_out) {
+                const Outlier* list = reinterpret_cast<const Outlier*>(image + ((static_cast<uint64_t>(blk->outlier_hi) << 32) | blk->outlier_lo));
+                for (uint32_t i = tid; i < n_out; i += kConsumerWaves * kWaveLanes) {
+                    const Outlier o = list[i];
+                    Rows<kFloat>::add(ys, o.row, Rows<kFloat>::product(o.value, x[o.col]));
+                }
+            }
+        }
         if (!loader) {
             const acc_t flushed = atomicAdd(ys + nrows, static_cast<acc_t>(0));
             asm volatile("" ::"v"(flushed));
@@ -892,6 +936,27 @@ __global__ __launch_bounds__(kThreads) void spmv_rowblock_kernel(const uint8_t* 
         timeline_stamp<kAblate>(block_no, wave, lane, 4);
         if (!next) break;
     }
+}
+
+template <bool kFloat, int kRing, int kAblate, int kDepth, bool kOwner = false>
+__global__ __launch_bounds__(kThreads) void spmv_rowblock_kernel(const uint8_t* __restrict__ image, const Block* __restrict__ blocks,
+                                                                  const Unit* __restrict__ units, const uint32_t* __restrict__ x,
+                                                                  uint32_t* __restrict__ out, int32_t row_part_filter, uint32_t ring,
+                                                                  uint32_t x_base, const uint32_t* __restrict__ part_heads, CarriedCombine carry) {
+    static_assert(!(kRing & 8), "DELTA with 24-bit value fields is spmv_rowblock_kernel_delta24");
+    rowblock_workgroup<kFloat, kRing, kAblate, kDepth, kOwner>(image, blocks, units, x, out, row_part_filter, ring, x_base, part_heads, carry);
+}
+
+// DELTA images with 24-bit value fields (stream_tiles.h: kRecordBytes24; fixed point only): the same workgroup over 640-byte records -- ring format 4
+// (RingT<4>: a dwordx2 and a 16-bit load per record), one shift per value word, and the block's outlier list in front of the flush.
+// (Named spmv_rowblock_kernel_...: profilers and bench.py find a matrix's dominant kernel by the substring "spmv_rowblock_kernel".)
+// kRes: the image stays in the Infinity Cache (`sc1` stream loads instead of `nt`), as kRing & 4 of spmv_rowblock_kernel.
+template <bool kRes, int kAblate>
+__global__ __launch_bounds__(kThreads) void spmv_rowblock_kernel_delta24(const uint8_t* __restrict__ image, const Block* __restrict__ blocks,
+                                                                 const Unit* __restrict__ units, const uint32_t* __restrict__ x,
+                                                                 uint32_t* __restrict__ out, int32_t row_part_filter, uint32_t ring,
+                                                                 uint32_t x_base, const uint32_t* __restrict__ part_heads, CarriedCombine carry) {
+    rowblock_workgroup<false, kRes ? 12 : 8, kAblate, 8>(image, blocks, units, x, out, row_part_filter, ring, x_base, part_heads, carry);
 }
 
 // Column-sliced matrices: y[r] = sum over slices of the per-slice partial results.  Fixed point: each partial is
@@ -1179,6 +1244,12 @@ uint32_t spmv_lds_bytes(uint32_t max_block_rows, uint32_t ring_buffers, uint32_t
 #define HS_FOR_EACH_PRODUCT_VARIANT(X)                                                                           \
     X(true, 0, 0, 8) X(true, 1, 0, 8) X(false, 0, 0, 8) X(false, 1, 0, 8) X(true, 2, 0, 8) X(false, 2, 0, 8)      \
     X(true, 4, 0, 8) X(true, 5, 0, 8) X(false, 4, 0, 8) X(false, 5, 0, 8)
+// spmv_rowblock_kernel_delta24 (resident, ablate): the two cache policies; the profiling library adds "no LDS accumulate" / "no LDS gather" / both under `nt`
+#ifndef HISPARSE_PROFILING
+#define HS_FOR_EACH_DELTA24_VARIANT(X) X(false, 0) X(true, 0)
+#else
+#define HS_FOR_EACH_DELTA24_VARIANT(X) X(false, 0) X(true, 0) X(false, 1) X(false, 2) X(false, 3)
+#endif
 #ifndef HISPARSE_PROFILING
 #define HS_FOR_EACH_VARIANT(X) HS_FOR_EACH_PRODUCT_VARIANT(X)
 #else
@@ -1196,6 +1267,12 @@ hipError_t configure_spmv_kernels(uint32_t lds_bytes) {
     hipError_t e;
 #define X(F, T, A, D) if ((e = configure_one<F, T, A, D>(lds_bytes)) != hipSuccess) return e;
     HS_FOR_EACH_VARIANT(X)
+#undef X
+#define X(R, A)                                                                                                                               \
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spmv_rowblock_kernel_delta24<R, A>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                 static_cast<int>(lds_bytes))) != hipSuccess)                                                                \
+        return e;
+    HS_FOR_EACH_DELTA24_VARIANT(X)
 #undef X
 #define X(A) if ((e = configure_one<true, false, A, 8, true>(lds_bytes)) != hipSuccess) return e;
     HS_FOR_EACH_OWNER_VARIANT(X)
@@ -1233,6 +1310,8 @@ hipError_t launch_spmv(bool is_float, const SpmvLaunch& a, hipStream_t stream) {
         return hipErrorInvalidValue;
     }
     int ring = a.format == kFormatDelta ? 1 : a.format == kFormatPairs24 ? 2 : 0;
+    const bool delta24 = a.format == kFormatDelta && a.value_bits == 24;
+    if (delta24 && is_float) return hipErrorInvalidValue;      // the packed record is fixed-point only
     const dim3 grid(a.num_workgroups), block(kThreads);
     const uint32_t x_base = a.lds_bytes - a.ring_buffers * kBufBytes;
     const CarriedCombine carry = carried(a);
@@ -1334,6 +1413,18 @@ hipError_t launch_spmv(bool is_float, const SpmvLaunch& a, hipStream_t stream) {
                 }
             }
         }
+        return launched ? hipGetLastError() : hipErrorInvalidValue;
+    }
+    if (delta24) {
+        const bool resident = (ring & 4) != 0;
+#define X(R, A)                                                                                                                      \
+    if (!launched && resident == R && ablate == A && depth == 8) {                                                                    \
+        hipLaunchKernelGGL((spmv_rowblock_kernel_delta24<R, A>), grid, block, a.lds_bytes, stream, a.image, a.blocks, a.units, a.x, a.out,      \
+                           a.row_part_filter, a.ring_buffers, x_base, a.part_heads, carry);                                          \
+        launched = true;                                                                                                             \
+    }
+        HS_FOR_EACH_DELTA24_VARIANT(X)
+#undef X
         return launched ? hipGetLastError() : hipErrorInvalidValue;
     }
 #define X(F, T, A, D)                                                                                                           \

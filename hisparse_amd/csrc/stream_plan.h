@@ -33,6 +33,7 @@ struct IntSwitch {      // an option that is read with std::atoi where it is set
 };
 struct PlanSwitches {
     ForcedFormat format = ForcedFormat::kNone;      // HISPARSE_STREAM_FORMAT (kInvalid: reported after pass 0 and the census, where it always was)
+    DeltaValueBits delta_bits = DeltaValueBits::kByRule;   // ... = delta24 / delta32: DELTA (kDelta above) with packed / plain value words whatever the rule says
     IntSwitch col_slices, max_rows, light, light_wgs, sweep, row_runs;
     bool spmm4 = false;             // HISPARSE_SPMM_VECTORS=4
     bool pow2_slices = false;       // HISPARSE_POW2_SLICES (set at all)
@@ -54,7 +55,9 @@ struct PlanSwitches {
         };
         if (const char* force = env_switch("HISPARSE_STREAM_FORMAT")) {
             const std::string f(force);
-            sw.format = f == "pairs" ? ForcedFormat::kPairs : f == "delta" ? ForcedFormat::kDelta : f == "owner" ? ForcedFormat::kOwner :
+            if (f == "delta24") sw.delta_bits = DeltaValueBits::kPacked;
+            if (f == "delta32") sw.delta_bits = DeltaValueBits::kPlain;
+            sw.format = f == "pairs" ? ForcedFormat::kPairs : (f == "delta" || f == "delta24" || f == "delta32") ? ForcedFormat::kDelta : f == "owner" ? ForcedFormat::kOwner :
                         f == "owner24" ? ForcedFormat::kOwner24 : f == "sweep" ? ForcedFormat::kSweep : f == "bitmap" ? ForcedFormat::kBitmap : ForcedFormat::kInvalid;
         }
         sw.col_slices = number("HISPARSE_COL_SLICES");
@@ -77,7 +80,7 @@ struct PlanSwitches {
         return sw;
     }
 };
-inline const char* const kBadStreamFormat = "HISPARSE_STREAM_FORMAT must be pairs, delta, owner, owner24, sweep or bitmap";
+inline const char* const kBadStreamFormat = "HISPARSE_STREAM_FORMAT must be pairs, delta, delta24, delta32, owner, owner24, sweep or bitmap";
 
 // ---- one copy of the rules that the census and the builder must apply alike -----------------------------------------------------------
 
@@ -538,6 +541,9 @@ inline TilePlan plan_row_blocks(const PlanInputs& in, double hub_share, DenseRow
 //    40000^2 and 400000 x 100000 power-law matrices at mean gaps 16 ... 4096, ogbl-ppa, mouse_gene):
 //    t(DELTA) - t(PAIRS) = (bytes saved) / 6.5 TB/s - c with c = 3.5 us fixed point, 6 us float (more instructions per element,
 //    a head record per unit and wavefront).  So: DELTA only when it saves more than kDeltaMinSavedBytes of stream.
+// (DELTA is priced at its PLAIN 768-byte record here, deliberately, also where the image will be packed into 640-byte records (stream_tiles.h:
+// kRecordBytes24): the constants above were fitted on plain images, and a matrix whose plain DELTA image misses the saving but whose packed one would
+// clear it -- a PAIRS image of 115 ... 140 MB -- has not been measured as a packed image against PAIRS.  Such a matrix stays PAIRS.)
 // Returns kFormatDelta or kFormatPairs for a tentative DELTA plan of `num_blocks` blocks.
 inline StreamFormat delta_or_pairs(const std::vector<UnitPlan>& plans, uint32_t num_blocks, uint64_t nnz, bool is_float) {
     uint64_t slots = 0, pairs_bytes = 0, delta_bytes = 0;

@@ -12,6 +12,7 @@
 #include "stream_plan.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -66,6 +67,8 @@ struct TileBuild {
     std::vector<uint32_t> block_of_unit;
     std::vector<uint64_t> block_nnz;      // weight of a block for the workgroup assignment
     uint64_t image_bytes = 0;
+    uint32_t record_bytes = kRecordBytes;   // DELTA: kRecordBytes24 once choose_value_bits has decided to pack
+    uint64_t outlier_count = 0;             // packed DELTA: value words that do not fit the field at the chosen shift
     std::vector<std::vector<uint32_t>> mine;
 
     TileBuild(const void* const channel_[NUM_HBM_CHANNELS], const uint64_t n_packets_[NUM_HBM_CHANNELS], const Geometry& geom, uint32_t num_rows_,
@@ -115,6 +118,8 @@ struct TileBuild {
     void fall_back_to_pairs();
     bool owner_shares(uint32_t max_span);
     bool lay_out_streams();
+    bool choose_value_bits();
+    void place_outliers(const std::vector<uint32_t>& unit, const std::vector<Outlier>& entry);
     void assign_to_workgroups();
     void finish_blocks();
     bool emit_on_gpu();
@@ -421,6 +426,7 @@ bool TileBuild::lay_out_streams() {
     const bool delta_spread = sw.delta_spread;
     block_nnz.assign(NB, 0);
     image_bytes = 0;
+    out.elements = 0;
     for (uint32_t bi = 0; bi < NB; ++bi) {
         Block& blk = out.blocks[bi];
         uint32_t pos[kConsumerWaves] = {0};   // chunk / record position of every wavefront in its stream
@@ -470,13 +476,13 @@ bool TileBuild::lay_out_streams() {
         for (uint32_t w = 0; w < kConsumerWaves; ++w) block_nnz[bi] += pos[w];   // the block's weight: wavefront steps, heads included
         // the kernel addresses a wavefront's stream with a 32-bit byte offset from Block::wave_offset
         for (uint32_t w = 0; w < kConsumerWaves; ++w)
-            if (uint64_t(pos[w]) * (delta ? kRecordBytes : owner ? chunk_bytes : wave_stride) >= (1ull << 32)) { error = "row block stream exceeds 4 GiB"; return false; }
+            if (uint64_t(pos[w]) * (delta ? record_bytes : owner ? chunk_bytes : wave_stride) >= (1ull << 32)) { error = "row block stream exceeds 4 GiB"; return false; }
         if (delta || owner) {      // every wavefront's steps are contiguous
             for (uint32_t w = 0; w < kConsumerWaves; ++w) {
                 blk.wave_offset[w] = image_bytes;
                 // OWNER24: whole records of four steps (the steps behind the last one are never consumed)
                 image_bytes += owner24 ? uint64_t((pos[w] + kOwnerRecordSteps - 1) / kOwnerRecordSteps) * kOwnerRecordBytes
-                                       : uint64_t(pos[w]) * (delta ? kRecordBytes : chunk_bytes);
+                                       : uint64_t(pos[w]) * (delta ? record_bytes : chunk_bytes);
             }
         } else {
             // chunks are stored in dealing order (global chunk g of the block at g * 512 bytes; wavefront w consumes
@@ -486,6 +492,63 @@ bool TileBuild::lay_out_streams() {
         }
     }
     return true;
+}
+
+// ---- DELTA: 24-bit value fields or plain 32-bit words (stream_tiles.h: kRecordBytes24)?  Called with the plain layout done; lays the streams out again
+//      when it packs.  The shift and the misfit count depend on the value words alone, so both builders agree before a byte is emitted. ----
+bool TileBuild::choose_value_bits() {
+    out.value_bits = 32;
+    out.value_shift = 0;
+    if (is_float || sw.delta_bits == DeltaValueBits::kPlain || (csr && (csr->value_map || csr->plain_values))) return true;
+    uint64_t misfits[kMaxValueShift + 1] = {0};
+    if (gpu) {
+        if (!gpu->count_value_misfits(misfits)) return gpu_failed();
+    } else {
+        std::vector<std::array<uint64_t, kMaxValueShift + 1>> part(out.units.size());
+        parallel_for(out.units.size(), [&](size_t u) {
+            part[u].fill(0);
+            const uint64_t* e = scratch.data() + plans[u].scratch;
+            for (uint32_t i = 0; i < plans[u].n; ++i)
+                for (uint32_t sh = 0; sh <= kMaxValueShift; ++sh) part[u][sh] += !value_fits24(uint32_t(e[i]), sh);
+        });
+        for (const auto& p : part)
+            for (uint32_t sh = 0; sh <= kMaxValueShift; ++sh) misfits[sh] += p[sh];
+    }
+    uint32_t shift = 0;
+    for (uint32_t sh = 1; sh <= kMaxValueShift; ++sh)
+        if (misfits[sh] < misfits[shift]) shift = sh;      // the fewest misfits; the smaller shift on a tie
+    const uint64_t plain_bytes = image_bytes, outliers = misfits[shift];
+    const uint64_t packed_bytes = plain_bytes / kRecordBytes * kRecordBytes24 + ((outliers * sizeof(Outlier) + 15u) & ~uint64_t(15));
+    const bool within_cap = outliers * kDelta24OutlierShare <= out.elements;
+    const bool wanted = sw.delta_bits == DeltaValueBits::kPacked || plain_bytes >= packed_bytes + kDelta24MinSavedBytes;
+    if (sw.debug)
+        std::fprintf(stderr, "delta value bits: shift %u leaves %llu outliers among %llu element slots, %llu -> %llu bytes: %s\n", shift, (unsigned long long)outliers,
+                     (unsigned long long)out.elements, (unsigned long long)plain_bytes, (unsigned long long)packed_bytes, within_cap && wanted ? "packed" : "plain");
+    if (!within_cap || !wanted) return true;
+    out.value_bits = 24;
+    out.value_shift = shift;
+    outlier_count = outliers;
+    record_bytes = kRecordBytes24;
+    if (!lay_out_streams()) return false;
+    image_bytes += (outliers * sizeof(Outlier) + 15u) & ~uint64_t(15);      // the outlier lists, behind the records
+    for (Block& blk : out.blocks) { blk.value_shift = shift; blk.value_bits = 24; }
+    return true;
+}
+
+// The outlier lists of a packed DELTA image: entry[k] belongs to unit unit[k]; the entries arrive in the order of the units and, inside a unit, of the
+// positions.  Blocks own contiguous unit ranges in block order, so the entries of one block are contiguous: its list is that stretch.
+void TileBuild::place_outliers(const std::vector<uint32_t>& unit, const std::vector<Outlier>& entry) {
+    const uint64_t lists = image_bytes - ((outlier_count * sizeof(Outlier) + 15u) & ~uint64_t(15));
+    for (size_t k = 0; k < entry.size(); ++k) {
+        Block& blk = out.blocks[block_of_unit[unit[k]]];
+        if (!blk.outlier_count) {
+            const uint64_t at = lists + k * sizeof(Outlier);
+            blk.outlier_lo = uint32_t(at);
+            blk.outlier_hi = uint32_t(at >> 32);
+        }
+        blk.outlier_count++;
+    }
+    out.outliers = entry.size();
 }
 
 // ---- workgroups: longest-processing-time assignment of blocks (tiles_common.h) ------------------------------
@@ -523,7 +586,12 @@ void TileBuild::finish_blocks() {
 }
 
 bool TileBuild::emit_on_gpu() {
-    if (!gpu->emit(out.format, image_bytes, image_slack, plans, block_of_unit, out.blocks, is_float)) return gpu_failed();
+    std::vector<uint32_t> outlier_unit;
+    std::vector<Outlier> outlier_entry;
+    if (!gpu->emit(out.format, image_bytes, image_slack, plans, block_of_unit, out.blocks, is_float, out.value_bits, out.value_shift, outlier_count, out.units, outlier_unit,
+                   outlier_entry))
+        return gpu_failed();
+    if (out.value_bits == 24) place_outliers(outlier_unit, outlier_entry);
     out.d_image = gpu->release_image();
     out.d_value_map = gpu->release_value_map();
     out.image_bytes = image_bytes;
@@ -605,6 +673,9 @@ void TileBuild::emit_pairs() {
 // ---- DELTA: lane l of wavefront w owns run_len[w] consecutive slots of the sorted unit --------------------------------
 void TileBuild::emit_delta() {
     uint8_t* image = out.image.data();
+    const bool packed = out.value_bits == 24;
+    const uint32_t shift = out.value_shift;
+    std::vector<std::vector<Outlier>> unit_outliers(packed ? out.units.size() : 0);
     parallel_for(out.units.size(), [&](size_t u) {
         const UnitPlan& up = plans[u];
         const Block& blk = out.blocks[block_of_unit[u]];
@@ -619,16 +690,40 @@ void TileBuild::emit_delta() {
             while (d > kMaxGap) { at += kBridgeAdvance; d -= kBridgeAdvance; gap[k] = kBridgeGap; val[k] = 0; after[k] = at; ++k; }
             at += uint32_t(d);
             gap[k] = uint16_t(d); val[k] = uint32_t(e[i]); after[k] = at; ++k;
+            if (packed && !value_fits24(val[k - 1], shift)) {      // an outlier: its slot carries 0, the full word goes to the block's list
+                unit_outliers[u].push_back(Outlier{at / kSubTileCols, out.units[u].col0 + at % kSubTileCols, val[k - 1]});
+                val[k - 1] = 0;
+            }
         }
         const uint16_t pad_gap = is_float ? kBridgeGap : 0;
         const uint32_t scratch_pos = blk.nrows * kSubTileCols;   // local row nrows = the scratch accumulator
         for (uint32_t w = 0; w < kConsumerWaves; ++w) {
             if (!up.run_len[w]) continue;
-            uint8_t* rec = image + blk.wave_offset[w] + uint64_t(up.start_record[w]) * kRecordBytes;
+            uint8_t* rec = image + blk.wave_offset[w] + uint64_t(up.start_record[w]) * record_bytes;
+            const uint32_t slots_in_records = (up.run_len[w] + 2) / 2 * 2;      // head + run, rounded up to whole records
+            if (packed) {
+                // slot q sits in record q / 2: the lane's 8 bytes at lane * 8 hold field A (bits 0-23), field B (24-47) and gap A (48-63), gap B lies at 512 + lane * 2
+                auto put_slot = [&](uint32_t q, uint32_t l, uint32_t field, uint32_t gap16) {
+                    uint8_t* r = rec + uint64_t(q / 2) * kRecordBytes24;
+                    uint64_t& word = reinterpret_cast<uint64_t*>(r)[l];
+                    if (q % 2 == 0) word |= uint64_t(field) | uint64_t(gap16) << 48;
+                    else { word |= uint64_t(field) << 24; reinterpret_cast<uint16_t*>(r + kWaveLanes * 8)[l] = uint16_t(gap16); }
+                };
+                for (uint32_t l = 0; l < kWaveLanes; ++l) {
+                    const uint64_t s0 = up.first_slot[w] + uint64_t(l) * up.lane_stride[w];
+                    const uint32_t head = s0 >= up.slots ? scratch_pos : (s0 == 0 ? uint32_t(e[0] >> 32) : after[s0 - 1]);
+                    put_slot(0, l, head & 0xffffffu, head >> 24);      // the head's position: field A | gap A << 24
+                    for (uint32_t j = 0; j < up.run_len[w]; ++j) {
+                        const uint64_t si = s0 + j;
+                        put_slot(j + 1, l, si < up.slots ? val[si] >> shift : 0u, si < up.slots ? gap[si] : pad_gap);
+                    }
+                    for (uint32_t q = up.run_len[w] + 1; q < slots_in_records; ++q) put_slot(q, l, 0u, pad_gap);      // the dead slot of an odd run
+                }
+                continue;
+            }
             // slot q of the run (q = 0: the head) sits in record q / 2, half q % 2: value word at (2 lane + half) * 4, gap at 512 + lane * 4 + half * 2
             auto value_at = [&](uint32_t q, uint32_t l) -> uint32_t& { return reinterpret_cast<uint32_t*>(rec + uint64_t(q / 2) * kRecordBytes)[2 * l + q % 2]; };
             auto gap_at = [&](uint32_t q, uint32_t l) -> uint16_t& { return reinterpret_cast<uint16_t*>(rec + uint64_t(q / 2) * kRecordBytes + kWaveLanes * 8)[2 * l + q % 2]; };
-            const uint32_t slots_in_records = (up.run_len[w] + 2) / 2 * 2;      // head + run, rounded up to whole records
             for (uint32_t l = 0; l < kWaveLanes; ++l) {
                 const uint64_t s0 = up.first_slot[w] + uint64_t(l) * up.lane_stride[w];
                 // position BEFORE the run's first slot; slot 0 carries gap 0 from the first element's own position
@@ -642,6 +737,14 @@ void TileBuild::emit_delta() {
             }
         }
     });
+    if (packed) {      // the outlier lists, behind the records: in the order of the units
+        std::vector<uint32_t> unit;
+        std::vector<Outlier> entry;
+        for (size_t u = 0; u < unit_outliers.size(); ++u)
+            for (const Outlier& o : unit_outliers[u]) { unit.push_back(uint32_t(u)); entry.push_back(o); }
+        place_outliers(unit, entry);
+        if (!entry.empty()) std::memcpy(image + image_bytes - ((outlier_count * sizeof(Outlier) + 15u) & ~uint64_t(15)), entry.data(), entry.size() * sizeof(Outlier));
+    }
     finish_blocks();
     timer.lap("emit DELTA");
 }
@@ -719,6 +822,7 @@ Attempt build_stream_tiles_attempt(const void* const channel[NUM_HBM_CHANNELS], 
     }
     if (wants_pairs24(b.plan, sw, out.max_block_rows)) b.set_format(kFormatPairs24);
     if (!b.lay_out_streams()) return Attempt::kFailed;
+    if (out.format == kFormatDelta && !b.choose_value_bits()) return Attempt::kFailed;
     b.assign_to_workgroups();
     if (b.gpu) return b.emit_on_gpu() ? Attempt::kDone : Attempt::kFailed;
     resize_zeroed(out.image, b.image_bytes);

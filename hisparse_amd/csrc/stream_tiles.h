@@ -54,6 +54,12 @@
 //     the few rows there are: 55.6 vs 38.9 us on mouse_gene).
 //     HISPARSE_STREAM_FORMAT=pairs|delta overrides (the parity tests run both on every case).
 //
+//     DELTA with 24-bit VALUE FIELDS (5 bytes per slot; fixed point only): the same slots in 640-byte records -- Q8.24 words below 1.0 have a zero top
+//       byte, so a lane's two value words and its first gap fit its 8 bytes and the second gap takes 2 more.  One shift per image makes the fields
+//       value words again, and the few words that do not fit any field go to a per-block OUTLIER list behind the records, which the consumers add
+//       after the block's last unit (kRecordBytes24 below has the layout and the rules).  ogbl-ppa: 233.3 instead of 280.0 MB, 5.7 bytes per non-zero.
+//       Taken by itself when it shrinks a fixed-point DELTA image by kDelta24MinSavedBytes or more; HISPARSE_STREAM_FORMAT=delta24|delta32 force.
+//
 // Markers, lane padding and partition headers of the CPSR image are gone in both formats.
 #ifndef HISPARSE_STREAM_TILES_H_
 #define HISPARSE_STREAM_TILES_H_
@@ -112,6 +118,34 @@ constexpr uint32_t kWaveStrideBytes = kChunkBytes * kConsumerWaves;   // chunks 
 // isolation).  A (unit, wavefront) run = its head (slot A of the first record: absolute start positions) + run_len slots, padded to
 // an even slot count with one dead slot (value 0; gap 0 in fixed point, a bridge in the float modes).
 constexpr uint32_t kRecordBytes = kWaveLanes * 2 * (4 + 2);
+// DELTA with 24-bit value fields (fixed point only; hs_stats::value_bits == 24).  Everything about DELTA stays -- dealing, head slot, bridges, padding,
+// end_step in records, contiguous records per wavefront -- only the record's bytes change: 640 instead of 768.  Each lane holds 10 bytes:
+//     8 bytes at lane * 8:        bits 0-23 value field A, bits 24-47 value field B, bits 48-63 gap A      one dwordx2 per lane
+//     2 bytes at 512 + lane * 2:  gap B                                                                    one 16-bit load per lane
+// value word = field << value_shift, one shift (0 .. kMaxValueShift) per image: the builders take the shift with the fewest MISFITS (a word w fits
+// when w >> shift < 2^24 and its low `shift` bits are zero; ties: the smaller shift), so Q8.24 words below 1.0 pack at shift 0 and integer-valued
+// matrices (1.0 .. 255.0) at shift 8.  The head slot's position is field A | gap A << 24 (blocks of up to 12 287 rows reach positions near 2^27).
+// A misfit keeps its slot with value field 0 (in fixed point 0 * x rounds to exactly 0: the row sum is unchanged) and is ALSO written to its block's
+// OUTLIER list, {local row, absolute column, full value word} (Outlier below), in the order of the block's units and of the positions inside a unit;
+// the lists lie behind the records, 16-byte aligned as a whole, and Block::outlier_lo / _hi / outlier_count say where a block's list is.  The kernel's
+// consumer threads walk the list after the block's last unit: one x[col] read from global memory, one product, one add into the row's accumulator each.
+// Packing is refused -- the plain 32-bit record kept -- in the float modes, when the value map of hs_update_values was asked for (an updated value may
+// not fit), and when the outliers exceed 1 per kDelta24OutlierShare element slots of the image (a condition, not a tuning constant: it keeps the side walk
+// below one record's worth of work per block on any image the rule accepts).
+// STREAM_FORMAT = delta24 packs wherever the matrix allows it, delta32 never; delta (and an unforced DELTA plan) packs when the image shrinks by at
+// least kDelta24MinSavedBytes.
+constexpr uint32_t kRecordBytes24 = kWaveLanes * (3 + 3 + 2 + 2);
+constexpr uint32_t kMaxValueShift = 8;
+constexpr uint64_t kDelta24OutlierShare = 4096;
+// kDelta24MinSavedBytes: the project's own price of a format change (kDeltaMinSavedBytes), under which every small image stays byte-identical.  Measured
+// (profiles/delta24_ab.txt, parent and child alternating on one box): ogbl-ppa, -46.7 MB: 54.6 -> 51.3 us per step; mouse_gene, -30.8 MB: -1.0 us; the R-MAT stand-in, -47 MB: kernel 56.0 -> 53.3 us (its hub rows do
+// not eat the gain); hollywood, -137 MB: 145.5 -> 134.8 us.  gplus
+// (-14.4 MB, below the constant) gained 0.9 us forced, measured in one direction only -- not enough to lower it.
+constexpr uint64_t kDelta24MinSavedBytes = 23u << 20;
+constexpr uint32_t delta_record_bytes(uint32_t value_bits) { return value_bits == 24 ? kRecordBytes24 : kRecordBytes; }
+constexpr bool value_fits24(uint32_t word, uint32_t shift) { return (word >> shift) < (1u << 24) && (word & ((1u << shift) - 1u)) == 0; }
+struct Outlier { uint32_t row, col, value; };                 // local row of the block, absolute column, the full value word
+enum class DeltaValueBits : uint32_t { kByRule = 0, kPacked = 24, kPlain = 32 };      // STREAM_FORMAT = delta | delta24 | delta32
 constexpr uint32_t kMaxGap = 0xfffeu;                         // largest position gap an element slot can carry
 constexpr uint32_t kBridgeGap = 0xffffu;                      // gap code of a slot without element ...
 constexpr uint32_t kBridgeAdvance = 0xffffu;                  // ... which advances the position by this much
@@ -134,9 +168,14 @@ enum StreamFormat : uint32_t { kFormatPairs = 0, kFormatDelta = 1, kFormatBitmap
 // taken for them by the SWEEP rule and has no effect (stream_policy_applies; hs_stats::stream_resident reports 0).
 constexpr bool rowblock_stream(uint32_t format, bool light) { return (format == kFormatPairs || format == kFormatDelta) && !light; }
 constexpr bool stream_policy_applies(uint32_t format, bool light) { return format == kFormatSweep || rowblock_stream(format, light); }
-constexpr bool plan_stream_resident(uint32_t format, bool light, uint64_t image_bytes, uint64_t num_units, uint64_t num_blocks) {
+// A packed DELTA image (value_bits == 24) is judged by the size of its PLAIN form, so that packing by itself never flips the policy: ogbl-ppa's
+// image shrinks from 267 to 222.5 MiB, under the cache's size, and would silently go from `nt` to `sc1` -- which on this matrix gained 1.5 % warm
+// and cost 14 % in the round-robin leg (above).  The rule: `nt` stays unless `sc1` wins both legs.  On the packed image only the warm leg was measured
+// (profiles/delta24_ab.txt: `sc1` -4.1 us of kernel time); its round-robin leg is unmeasured, so `nt` stays.
+constexpr bool plan_stream_resident(uint32_t format, bool light, uint64_t image_bytes, uint64_t num_units, uint64_t num_blocks, uint32_t value_bits = 0) {
+    const uint64_t judged_bytes = format == kFormatDelta && value_bits == 24 ? image_bytes / kRecordBytes24 * kRecordBytes : image_bytes;
     return rowblock_stream(format, light)
-               ? image_bytes <= kRowblockResidentMaxImageBytes && (num_units > num_blocks || image_bytes <= kRowblockResidentSmallImageBytes)
+               ? judged_bytes <= kRowblockResidentMaxImageBytes && (num_units > num_blocks || judged_bytes <= kRowblockResidentSmallImageBytes)
                : image_bytes <= kResidentMaxImageBytes;
 }
 // The combine pass carried into the next step's kernel (hs_context.h: CarriedCombine), for plans of several column slices.
@@ -275,7 +314,11 @@ struct Block {
     uint32_t first_col0, first_ncols;       // == units[unit_begin].col0 / .ncols (0 / 0 for a block without units)
     uint32_t last_part;     // row partition of the block's LAST row (>= row_part: since round 5 a row range may cross partition borders)
     uint32_t next_part;     // row_part of the workgroup's next block, 0xffffffff: none -- a run of partition p (hs_run_partition) goes on while next_part <= p
-    uint32_t pad[12];
+    uint32_t outlier_lo, outlier_hi;   // packed DELTA images (kRecordBytes24): byte offset of the block's outlier list in the image ...
+    uint32_t outlier_count;            // ... and its length (0 in every other image, like the words behind it)
+    uint32_t value_shift;              // packed DELTA images: value word = 24-bit field << value_shift (the same in every block of an image)
+    uint32_t value_bits;               // 24 in every block of a packed DELTA image, 0 everywhere else (hs_debug_read_tiles / hs_tiles_copy hand the two out this way)
+    uint32_t pad[7];
 };
 struct Unit {
     uint32_t col0;          // first absolute column of the x sub-tile
@@ -355,6 +398,9 @@ struct StreamTiles {
     uint32_t col_slices = 1;             // > 1: blocks write per-slice partial results, a combine pass adds them
     uint32_t ring_buffers = kMaxXBuffers;
     StreamFormat format = kFormatPairs;
+    uint32_t value_bits = 0;             // DELTA: 24 (packed records, kRecordBytes24) or 32; 0 for every other format
+    uint32_t value_shift = 0;            // packed DELTA: value word = field << value_shift
+    uint64_t outliers = 0;               // packed DELTA: entries of the outlier lists behind the records
     uint64_t nnz = 0;
     uint64_t elements = 0;               // element slots including bridges and chunk padding (DELTA head records not counted)
 };
@@ -368,6 +414,8 @@ struct CsrView {
     const uint32_t* indices = nullptr;
     const float* values = nullptr;
     bool value_map = false;                  // option value_map: the device builder also records every non-zero's value word index (gpu_tiles.h)
+    bool plain_values = false;               // the value map was asked for, whether or not THIS load builds it (autotune's candidate loads do not): a DELTA
+                                             // image keeps 32-bit value words, so that a candidate is timed as the image the kept load will have
     // hs_load_matrix_csr_transposed: the fields above describe the ARRAYS (a matrix A); the matrix to build is A^T, num_cols x num_rows.
     // The device builder swaps the roles of row and column element by element (gpu_tiles.h), no transposed copy exists; a value map
     // stays in the order of the arrays.  A host builder sees A^T's own CSR through detail::HostCsr (tiles_common.h).

@@ -33,7 +33,7 @@ class Stats(C.Structure):
     _fields_ = [("nnz", C.c_uint64), ("cpsr_bytes", C.c_uint64), ("stream_bytes", C.c_uint64), ("stream_elements", C.c_uint64),
                 ("num_blocks", C.c_uint32), ("num_units", C.c_uint32), ("num_workgroups", C.c_uint32), ("lds_bytes", C.c_uint32),
                 ("num_compute_units", C.c_uint32), ("col_slices", C.c_uint32), ("ring_buffers", C.c_uint32), ("stream_format", C.c_uint32),
-                ("load_seconds", C.c_double), ("retiled_on_gpu", C.c_uint32), ("light_kernel", C.c_uint32), ("stream_resident", C.c_uint32), ("reserved0", C.c_uint32)]
+                ("load_seconds", C.c_double), ("retiled_on_gpu", C.c_uint32), ("light_kernel", C.c_uint32), ("stream_resident", C.c_uint32), ("value_bits", C.c_uint32)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -45,7 +45,17 @@ CONSUMER_WAVES = 14
 BLOCK_DTYPE = np.dtype([("row0", "<u4"), ("nrows", "<u4"), ("row_part", "<u4"), ("unit_begin", "<u4"), ("unit_end", "<u4"),
                         ("flags", "<u4"), ("out_offset", "<u4"), ("next", "<u4"), ("wave_offset", "<u8", (CONSUMER_WAVES,)),
                         ("total_steps", "<u4", (CONSUMER_WAVES,)), ("first_end", "<u4", (CONSUMER_WAVES,)), ("first_col0", "<u4"),
-                        ("first_ncols", "<u4"), ("last_part", "<u4"), ("next_part", "<u4"), ("pad", "<u4", (12,))])
+                        ("first_ncols", "<u4"), ("last_part", "<u4"), ("next_part", "<u4"),
+                        ("outlier_lo", "<u4"), ("outlier_hi", "<u4"), ("outlier_count", "<u4"), ("value_shift", "<u4"), ("value_bits", "<u4"), ("pad", "<u4", (7,))])
+OUTLIER_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("value", "<u4")])   # packed DELTA images: an entry of a block's outlier list
+
+
+def _delta_value_bits(fmt, blocks):
+    """(value_bits, value_shift) of an image from its format name and Block table: 24 / 32 for DELTA (packed / plain value words), else 0."""
+    if fmt != "delta":
+        return 0, 0
+    packed = len(blocks) > 0 and int(blocks["value_bits"][0]) == 24
+    return (24, int(blocks["value_shift"][0])) if packed else (32, 0)
 UNIT_DTYPE = np.dtype([("col0", "<u4"), ("ncols", "<u4"), ("end_step", "<u4", (CONSUMER_WAVES,))])
 
 
@@ -241,14 +251,15 @@ class SpmvEngine:
         return y
 
     def read_tiles(self):
-        """What hs_load_matrix left on the device: dict(image, blocks, units) (tests compare it with build_tiles)."""
+        """What hs_load_matrix left on the device: dict(image, blocks, units, value_bits, value_shift) (tests compare it with build_tiles)."""
         st = self.stats()
         nbytes, nblocks, nunits = st["stream_bytes"], st["num_blocks"], st["num_units"]
         image = np.zeros(max(nbytes, 1), dtype=np.uint8)
         blocks = np.zeros(max(nblocks, 1), dtype=BLOCK_DTYPE)
         units = np.zeros(max(nunits, 1), dtype=UNIT_DTYPE)
         self._check(lib().hs_debug_read_tiles(self._h, image.ctypes.data, image.size, blocks.ctypes.data, units.ctypes.data))
-        return dict(image=image[:nbytes], blocks=blocks[:nblocks], units=units[:nunits])
+        bits, shift = _delta_value_bits(STREAM_FORMATS[st["stream_format"]], blocks[:nblocks])
+        return dict(image=image[:nbytes], blocks=blocks[:nblocks], units=units[:nunits], value_bits=bits, value_shift=shift)
 
     def read_mfma_image(self):
         """The second image of a float BITMAP matrix (SpMM on the matrix engine), as bytes; empty when there is none."""
@@ -391,7 +402,8 @@ def build_tiles(packets, impl, ob_bank, vb_bank, num_rows, num_cols, num_row_par
         mfma = np.zeros(max(mbytes.value, 1), dtype=np.uint8)
         if mbytes.value:
             l.hs_tiles_mfma(h, mfma.ctypes.data, mfma.size, None, None, None)
-        return dict(image=image[:nbytes.value], blocks=blocks[:nblocks.value], units=units[:nunits.value], wg_first=wg_first,
+        bits, shift = _delta_value_bits(STREAM_FORMATS[fmt.value], blocks[:nblocks.value])
+        return dict(image=image[:nbytes.value], blocks=blocks[:nblocks.value], units=units[:nunits.value], wg_first=wg_first, value_bits=bits, value_shift=shift,
                     block_order=order[:nblocks.value], num_workgroups=nwg.value, max_block_rows=maxrows.value, nnz=nnz.value,
                     elements=elems.value, col_slices=slices.value, ring_buffers=ring.value,
                     format=STREAM_FORMATS[fmt.value], mfma=mfma[:mbytes.value], mfma_chunk=chunk.value, mfma_chunks=chunks.value)

@@ -1,6 +1,8 @@
 """CPU only (the host builder, hs_tiles_build): the plan the library takes for the reference's matrices and for the out-of-sample cases of
 tools/planner_check.py, WITH the tile census (round 6) and with HISPARSE_PLAN_CENSUS=0 (the planner of rounds 1-5) -- which plans changed?
-    python tools/plan_diff.py [dataset names / planner_check case names ...]"""
+    python tools/plan_diff.py [dataset names / planner_check case names ...]
+A DELTA plan is printed with its value bits (delta/24: packed 640-byte records, delta/32: plain); HISPARSE_STREAM_FORMAT=delta24 | delta32 in the
+environment forces either, like every other format."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,7 +22,7 @@ def plan(csr, impl):
         os.environ["HISPARSE_PLAN_CENSUS"] = census
         t0 = time.perf_counter()
         t = device.build_tiles(cp, impl, cp.ob_bank, cp.vb_bank, cp.num_rows, cp.num_cols, cp.num_row_partitions, cp.num_col_partitions, 256)
-        out[census] = (f"{t['format']} x{t['col_slices']}, {len(t['blocks'])} blocks, {len(t['units'])} units, {len(t['image'])/1e6:.0f} MB", time.perf_counter() - t0)
+        out[census] = (f"{t['format']}{'/%d' % t['value_bits'] if t['value_bits'] else ''} x{t['col_slices']}, {len(t['blocks'])} blocks, {len(t['units'])} units, {len(t['image'])/1e6:.0f} MB", time.perf_counter() - t0)
     return out
 
 

@@ -36,7 +36,7 @@ def V(tag, impl, env=None, wgs=256, banks=None, mutate=None):
 
 
 def forced_variants(impl):
-    f = [V(f"format={x}", impl, {"STREAM_FORMAT": x}) for x in ("pairs", "delta", "owner", "owner24", "bitmap", "sweep")]
+    f = [V(f"format={x}", impl, {"STREAM_FORMAT": x}) for x in ("pairs", "delta", "delta24", "delta32", "owner", "owner24", "bitmap", "sweep")]
     f += [V("aux_bits=24", impl, {"AUX_BITS": "24"}), V("aux_bits=24,format=pairs", impl, {"AUX_BITS": "24", "STREAM_FORMAT": "pairs", "COL_SLICES": "1"})]
     f += [V(f"col_slices={s}", impl, {"COL_SLICES": str(s)}) for s in (1, 2, 4, 7)]
     f += [V("max_rows=64", impl, {"MAX_ROWS": "64"}), V("max_rows=64,light=1", impl, {"MAX_ROWS": "64", "LIGHT": "1"}), V("light=0", impl, {"LIGHT": "0"}),
