@@ -12,6 +12,7 @@
 #include "device_buffer.h"
 #include "hsw_common.h"
 #include "wide_products.h"
+#include "wide_schedule.h"
 
 namespace {
 
@@ -58,17 +59,6 @@ int enter(hsw_pattern* p) {
     if (!p) return HS_ERR_BAD_ARG;
     HSW_HIP(p, hipSetDevice(p->device));
     return HS_OK;
-}
-
-// every row class by class (wide_products.h); the long rows (class 0, started first) longest first, the others ascending
-void schedule(uint32_t rows, const uint32_t* ptr, std::vector<uint32_t>& list, uint32_t (&count)[kWideClasses]) {
-    std::fill(count, count + kWideClasses, 0u);
-    for (uint32_t r = 0; r < rows; ++r) ++count[wide_class_of(ptr[r + 1] - ptr[r])];
-    uint32_t next[kWideClasses];
-    for (uint32_t c = 0, at = 0; c < kWideClasses; at += count[c++]) next[c] = at;
-    list.resize(rows);
-    for (uint32_t r = 0; r < rows; ++r) list[next[wide_class_of(ptr[r + 1] - ptr[r])]++] = r;
-    std::stable_sort(list.begin(), list.begin() + count[0], [&](uint32_t a, uint32_t b) { return ptr[a + 1] - ptr[a] > ptr[b + 1] - ptr[b]; });
 }
 
 // one side's arrays onto the device; mapped: the side has a perm array (of nnz words, like idx)

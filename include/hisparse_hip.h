@@ -302,7 +302,9 @@ int hs_load_matrix_csr_transposed(hs_context* ctx, uint32_t num_rows, uint32_t n
  * matrix again with the new values, or leave the dense dispatch off.
  * (The product that MAKES such values in this order, dW[e] = sum_j U_j[row(e)] V_j[col(e)], is an object of its own: hisparse_pattern.h.
  * Callers whose values change on EVERY step and whose dense operands are row-major node features, [index][feature], need neither this
- * call nor a context for the products with those values: hisparse_wide.h reads the values from a device array in CSR order on each call.) */
+ * call nor a context for the products with those values: hisparse_wide.h reads the values from a device array in CSR order on each call,
+ * and hisparse_attention.h does the whole attention step forward -- scores, row softmax, weighted sum -- in one call without any per-entry
+ * array.) */
 int hs_update_values(hs_context* ctx, const float* values, uint64_t nnz);
 int hs_update_values_device(hs_context* ctx, const float* values_dev, uint64_t nnz);
 
