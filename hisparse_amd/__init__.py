@@ -6,6 +6,7 @@ Layout:
   rows.py      ctypes face of include/hisparse_rows.h (the row softmax over a CSR pattern, forward and backward)
   wide.py      ctypes face of include/hisparse_wide.h (SDDMM, SpMM and transposed SpMM over a CSR pattern, row-major features)
   attention.py ctypes face of include/hisparse_attention.h (scores, row softmax and weighted sum over a CSR pattern in one call)
+  attention_backward.py ctypes face of include/hisparse_attention_backward.h (the backward of that step, from lse to gQ, gK and gV)
   datasets.py  the reference's benchmark matrices as seeded stand-ins
   sharding.py  row-block sharding of one matrix across the GPUs of a node (+ RCCL gather of y)
   csrc/        C++ / HIP sources of the two libraries and the `benchmark` driver
@@ -16,5 +17,6 @@ from . import datasets  # noqa: F401
 from . import rows  # noqa: F401
 from . import wide  # noqa: F401
 from . import attention  # noqa: F401
+from . import attention_backward  # noqa: F401
 
-__all__ = ["host", "device", "datasets", "rows", "wide", "attention"]
+__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward"]

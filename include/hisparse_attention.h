@@ -18,6 +18,7 @@
  * lse, the row's log-sum-exp, is one word per row: P[e] = exp(t[e] - lse[row(e)]) recomputes the probabilities later, and two partial
  * attentions over disjoint column slabs merge through their lse words.  The BACKWARD step has no fused call yet: recompute S and P with
  * hsw_sddmm_device + hsr_softmax_device and run the five calls of hisparse_wide.h's chain.
+ * (hisparse_attention_backward.h, added later, is that fused call: it reads lse and gives the three gradients in two launches.)
  *
  * ALL FEATURES ARE fp32, 1 <= d <= 256, and there is no impl argument, as in hisparse_wide.h.  Same library (libhisparse_hip.so;
  * libhisparse_cpu.so exports the same eight symbols on the host: plain loops on the calling thread, two passes per row, "device"
