@@ -7,6 +7,7 @@ Layout:
   wide.py      ctypes face of include/hisparse_wide.h (SDDMM, SpMM and transposed SpMM over a CSR pattern, row-major features)
   attention.py ctypes face of include/hisparse_attention.h (scores, row softmax and weighted sum over a CSR pattern in one call)
   attention_backward.py ctypes face of include/hisparse_attention_backward.h (the backward of that step, from lse to gQ, gK and gV)
+  heads.py     ctypes face of include/hisparse_heads.h (multi-head attention over a CSR pattern, forward and backward, all heads per call)
   datasets.py  the reference's benchmark matrices as seeded stand-ins
   sharding.py  row-block sharding of one matrix across the GPUs of a node (+ RCCL gather of y)
   csrc/        C++ / HIP sources of the two libraries and the `benchmark` driver
@@ -18,5 +19,6 @@ from . import rows  # noqa: F401
 from . import wide  # noqa: F401
 from . import attention  # noqa: F401
 from . import attention_backward  # noqa: F401
+from . import heads  # noqa: F401
 
-__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward"]
+__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads"]

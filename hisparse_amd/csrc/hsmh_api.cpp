@@ -1,0 +1,256 @@
+// hsmh_api.cpp — include/hisparse_heads.h on the HIP runtime: the pattern object of the multi-head attention step, forward and backward.
+// As hsat_api.cpp's and hsab_api.cpp's, one object owns one device, one stream of its own and, from hsmh_create on, all the device
+// memory its _device calls will ever use (device_buffer.h): the CSR arrays with the rows sorted into the length classes of
+// wide_products.h (wide_schedule.h) and, with HSMH_BACKWARD, the transposed pattern (hsw_common.h's stable counting sort, without its
+// CSR-index map) with the columns sorted the same way and max_heads doubles per row, the D words the row kernel writes and the column
+// kernel reads.  The kernels are in heads_attention.hip.  Nothing here touches a context or another pattern object.
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "device_buffer.h"
+#include "heads_attention.h"
+#include "hsmh_common.h"
+#include "wide_schedule.h"
+
+using namespace hisparse::dev;
+
+struct hsmh_pattern {
+    int device = 0;
+    uint32_t num_rows = 0, num_cols = 0, max_heads = 0;
+    bool backward = false;
+    uint64_t nnz = 0;
+    uint64_t device_bytes = 0;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    DeviceBuffer<uint32_t> ptr, idx, list;         // the pattern and its rows by class
+    DeviceBuffer<uint32_t> cptr, crow, clist;      // with HSMH_BACKWARD: the transposed pattern and its columns by class
+    DeviceBuffer<double> dsum;                     // with HSMH_BACKWARD: D per row and head, [row][max_heads]: one backward call in flight per object
+    WideSide rows, cols;
+    std::string error;
+};
+
+namespace {
+
+thread_local std::string g_create_error;
+
+int fail(hsmh_pattern* p, int code, const std::string& msg) {
+    if (p) p->error = msg; else g_create_error = msg;
+    return code;
+}
+int hip_fail(hsmh_pattern* p, hipError_t e, const char* what) { return fail(p, HS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+
+#define HSMH_HIP(p, call)                                             \
+    do {                                                              \
+        const hipError_t e_ = (call);                                 \
+        if (e_ != hipSuccess) return hip_fail((p), e_, #call);        \
+    } while (0)
+
+int enter(hsmh_pattern* p) {
+    if (!p) return HS_ERR_BAD_ARG;
+    HSMH_HIP(p, hipSetDevice(p->device));
+    return HS_OK;
+}
+
+// everything hsmh_create does on the device; the caller destroys p when this fails
+int build(hsmh_pattern* p, const uint32_t* indptr, const uint32_t* indices) {
+    HSMH_HIP(p, hipSetDevice(p->device));
+    HSMH_HIP(p, hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
+    p->stream = p->own_stream;
+    std::vector<uint32_t> list;
+    schedule(p->num_rows, indptr, list, p->rows.count);
+    const size_t ptr_bytes = (size_t(p->num_rows) + 1) * 4, entry_bytes = std::max<size_t>(size_t(p->nnz), 1) * 4, list_bytes = size_t(p->num_rows) * 4;
+    HSMH_HIP(p, p->ptr.alloc(ptr_bytes));
+    HSMH_HIP(p, p->idx.alloc(entry_bytes));
+    HSMH_HIP(p, p->list.alloc(list_bytes));
+    p->device_bytes = ptr_bytes + entry_bytes + list_bytes;
+    HSMH_HIP(p, hipMemcpyAsync(p->ptr.get(), indptr, ptr_bytes, hipMemcpyHostToDevice, p->own_stream));
+    HSMH_HIP(p, hipMemcpyAsync(p->list.get(), list.data(), list_bytes, hipMemcpyHostToDevice, p->own_stream));
+    if (p->nnz) HSMH_HIP(p, hipMemcpyAsync(p->idx.get(), indices, size_t(p->nnz) * 4, hipMemcpyHostToDevice, p->own_stream));
+    std::vector<uint32_t> cptr, crow, clist;      // alive until the synchronisation below
+    if (p->backward) {
+        {
+            std::vector<uint32_t> perm;      // the CSR index of every entry in column order: built by the shared sort, not kept
+            hisparse::hsw::build_transposed(p->num_rows, p->num_cols, indptr, indices, cptr, crow, perm);
+        }
+        schedule(p->num_cols, cptr.data(), clist, p->cols.count);
+        const size_t cptr_bytes = (size_t(p->num_cols) + 1) * 4, clist_bytes = size_t(p->num_cols) * 4, dsum_bytes = size_t(p->num_rows) * p->max_heads * 8;
+        HSMH_HIP(p, p->cptr.alloc(cptr_bytes));
+        HSMH_HIP(p, p->crow.alloc(entry_bytes));
+        HSMH_HIP(p, p->clist.alloc(clist_bytes));
+        HSMH_HIP(p, p->dsum.alloc(dsum_bytes));
+        p->device_bytes += cptr_bytes + entry_bytes + clist_bytes + dsum_bytes;
+        HSMH_HIP(p, hipMemcpyAsync(p->cptr.get(), cptr.data(), cptr_bytes, hipMemcpyHostToDevice, p->own_stream));
+        HSMH_HIP(p, hipMemcpyAsync(p->clist.get(), clist.data(), clist_bytes, hipMemcpyHostToDevice, p->own_stream));
+        if (p->nnz) HSMH_HIP(p, hipMemcpyAsync(p->crow.get(), crow.data(), size_t(p->nnz) * 4, hipMemcpyHostToDevice, p->own_stream));
+    }
+    HSMH_HIP(p, hipStreamSynchronize(p->own_stream));      // the host arrays (the caller's and the vectors here) are free again
+    p->rows.ptr = p->ptr.get();
+    p->rows.idx = p->idx.get();
+    p->rows.list = p->list.get();
+    p->cols.ptr = p->cptr.get();
+    p->cols.idx = p->crow.get();
+    p->cols.list = p->clist.get();
+    p->rows.entries = p->cols.entries = p->nnz;
+    return HS_OK;
+}
+
+// A dense host operand of n rows x w words on the device, ld = w (a multiple of 4)
+int features_in(hsmh_pattern* p, DeviceBuffer<float>& dev, const float* host, uint32_t n, uint32_t w) {
+    HSMH_HIP(p, dev.alloc_count(size_t(n) * w, 16));
+    HSMH_HIP(p, hipMemcpyAsync(dev.get(), host, size_t(n) * w * 4, hipMemcpyHostToDevice, p->stream));
+    return HS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hsmh_create(hsmh_pattern** out, int device_id, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, uint32_t max_heads, uint32_t flags) {
+    if (!out) return fail(nullptr, HS_ERR_BAD_ARG, "null pattern pointer");
+    *out = nullptr;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_create(num_rows, num_cols, indptr, indices, max_heads, flags, why)) return fail(nullptr, rc, why);
+    int count = 0;
+    hipError_t e = hipGetDeviceCount(&count);
+    if (e != hipSuccess || count <= 0) return fail(nullptr, HS_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
+    if (device_id < 0 || device_id >= count) return fail(nullptr, HS_ERR_BAD_ARG, "device_id out of range");
+    hipDeviceProp_t prop;
+    if ((e = hipGetDeviceProperties(&prop, device_id)) != hipSuccess) return hip_fail(nullptr, e, "hipGetDeviceProperties");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(nullptr, HS_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library carries gfx950 code only");
+    hsmh_pattern* p = new (std::nothrow) hsmh_pattern;
+    if (!p) return fail(nullptr, HS_ERR_NO_MEMORY, "out of memory");
+    p->device = device_id;
+    p->num_rows = num_rows;
+    p->num_cols = num_cols;
+    p->max_heads = max_heads;
+    p->backward = (flags & HSMH_BACKWARD) != 0;
+    p->nnz = indptr[num_rows];
+    p->rows.compute_units = p->cols.compute_units = uint32_t(prop.multiProcessorCount);
+    if (int rc = build(p, indptr, indices)) {
+        g_create_error = p->error;
+        if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return HS_OK;
+}
+
+int hsmh_destroy(hsmh_pattern* p) {
+    if (!p) return HS_OK;
+    (void)hipSetDevice(p->device);
+    // only the object's own stream is known to be alive; a caller-owned stream must have been synchronised by its owner
+    if (p->own_stream) {
+        (void)hipStreamSynchronize(p->own_stream);
+        (void)hipStreamDestroy(p->own_stream);
+    }
+    delete p;
+    return HS_OK;
+}
+
+const char* hsmh_last_error(const hsmh_pattern* p) { return p ? p->error.c_str() : g_create_error.c_str(); }
+
+int hsmh_info(const hsmh_pattern* p, uint64_t* nnz, uint64_t* device_bytes) {
+    if (!p) return HS_ERR_BAD_ARG;
+    if (nnz) *nnz = p->nnz;
+    if (device_bytes) *device_bytes = p->device_bytes;
+    return HS_OK;
+}
+
+int hsmh_set_stream(hsmh_pattern* p, void* hip_stream) {
+    if (!p) return HS_ERR_BAD_ARG;
+    p->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : p->own_stream;
+    return HS_OK;
+}
+
+int hsmh_sync(hsmh_pattern* p) {
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, hipStreamSynchronize(p->stream));
+    return HS_OK;
+}
+
+int hsmh_forward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, uint32_t heads, uint32_t d, float scale,
+                        float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward(p->num_rows, p->num_cols, p->max_heads, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_heads_forward(p->rows, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl, p->stream));
+    return HS_OK;
+}
+
+int hsmh_forward(hsmh_pattern* p, const float* q, const float* k, const float* v, uint32_t heads, uint32_t d, float scale, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_host(p->num_rows, p->num_cols, p->max_heads, q, k, v, heads, d, scale, y, lse, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<float> d_q, d_k, d_v, d_y, d_lse;      // transient (the host form is synchronous and may allocate)
+    if (int rc = features_in(p, d_q, q, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_k, k, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_v, v, p->num_cols, w)) return rc;
+    HSMH_HIP(p, d_y.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_lse.alloc_count(size_t(p->num_rows) * heads, 16));
+    int rc = hsmh_forward_device(p, d_q.get(), w, d_k.get(), w, d_v.get(), w, heads, d, scale, d_y.get(), w, lse ? d_lse.get() : nullptr, heads);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(y, d_y.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess && lse) e = hipMemcpyAsync(lse, d_lse.get(), size_t(p->num_rows) * heads * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+int hsmh_backward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* gy_dev, uint64_t ldgy,
+                         const float* lse_dev, uint64_t ldl, uint32_t heads, uint32_t d, float scale, float* gq_dev, uint64_t ldgq, float* gk_dev, uint64_t ldgk, float* gv_dev,
+                         uint64_t ldgv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward(p->num_rows, p->num_cols, p->max_heads, p->backward, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale,
+                                                gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_heads_backward_rows(p->rows, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale, gq_dev, ldgq, p->dsum.get(), p->max_heads,
+                                           p->stream));
+    HSMH_HIP(p, launch_heads_backward_cols(p->cols, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, p->dsum.get(), p->max_heads, heads, d, scale, gk_dev, ldgk, gv_dev,
+                                           ldgv, p->stream));
+    return HS_OK;
+}
+
+int hsmh_backward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* gy, const float* lse, uint32_t heads, uint32_t d, float scale, float* gq, float* gk,
+                  float* gv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_host(p->num_rows, p->num_cols, p->max_heads, p->backward, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<float> d_q, d_k, d_v, d_gy, d_lse, d_gq, d_gk, d_gv;      // transient (the host form is synchronous and may allocate)
+    if (int rc = features_in(p, d_q, q, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_k, k, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_v, v, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_gy, gy, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_lse, lse, p->num_rows, heads)) return rc;
+    HSMH_HIP(p, d_gq.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_gk.alloc_count(size_t(p->num_cols) * w, 16));
+    HSMH_HIP(p, d_gv.alloc_count(size_t(p->num_cols) * w, 16));
+    int rc = hsmh_backward_device(p, d_q.get(), w, d_k.get(), w, d_v.get(), w, d_gy.get(), w, d_lse.get(), heads, heads, d, scale, d_gq.get(), w, d_gk.get(), w, d_gv.get(), w);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(gq, d_gq.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gk, d_gk.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gv, d_gv.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+}  // extern "C"

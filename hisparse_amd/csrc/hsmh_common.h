@@ -1,0 +1,140 @@
+// hsmh_common.h — what the two implementations of include/hisparse_heads.h share (hsmh_api.cpp on the HIP runtime, hsmh_cpu.cpp on the
+// host): the argument checks, so that both refuse the same calls with the same codes.  Built from hsat_common.h's checks (the pattern,
+// scale, the reach of an operand), hsab_common.h's overlap check of the backward and hsw_common.h's checks of one operand, all taken at
+// the width heads * d.  Host code only.
+#ifndef HISPARSE_HSMH_COMMON_H_
+#define HISPARSE_HSMH_COMMON_H_
+
+#include <cstdint>
+#include <string>
+
+#include "hisparse_heads.h"
+#include "hsab_common.h"
+
+namespace hisparse {
+namespace hsmh {
+
+constexpr uint32_t kMaxHeads = 64;
+constexpr uint32_t kMaxWidth = 256;      // heads * d
+
+// hsmh_create's arguments and the pattern itself: hsat_create's check, max_heads and the flags
+inline int check_create(uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, uint32_t max_heads, uint32_t flags, std::string& why) {
+    if (flags & ~uint32_t(HSMH_BACKWARD)) {
+        why = "unknown flag bits (HSMH_BACKWARD = 1 is the only one)";
+        return HS_ERR_BAD_ARG;
+    }
+    if (max_heads < 1 || max_heads > kMaxHeads) {
+        why = "max_heads must be 1 ... 64";
+        return HS_ERR_BAD_ARG;
+    }
+    return hsat::check_create(num_rows, num_cols, indptr, indices, why);
+}
+
+// the SHAPES ACCEPTED paragraph of the header
+inline int check_shape(uint32_t heads, uint32_t d, uint32_t max_heads, std::string& why) {
+    const char* other = "; the per-head calls of hsat_forward_device / hsab_backward_device cover every other shape";
+    if (d < 4 || d > kMaxWidth || (d & (d - 1))) {
+        why = std::string("d must be one of 4, 8, 16, 32, 64, 128, 256") + other;
+        return HS_ERR_BAD_ARG;
+    }
+    if (heads < 1 || heads > max_heads) {
+        why = std::string("heads must be 1 ... max_heads, the count given to hsmh_create") + other;
+        return HS_ERR_BAD_ARG;
+    }
+    if (uint64_t(heads) * d > kMaxWidth) {
+        why = std::string("heads * d must be at most 256") + other;
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+// lse: num_rows rows of ldl words, `heads` of them used
+inline int check_lse(const float* lse, uint64_t ldl, uint32_t heads, std::string& why) {
+    if (int rc = hsw::check_entries("lse", lse, why)) return rc;
+    if (ldl < heads) {
+        why = "the leading dimension of lse must be at least heads";
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+inline uint64_t lse_reach(uint64_t n, uint64_t ldl, uint32_t heads) { return n ? ((n - 1) * ldl + heads) * 4 : 0; }
+
+// hsmh_forward_device's arguments
+inline int check_forward(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv,
+                         uint32_t heads, uint32_t d, float scale, const float* y, uint64_t ldy, const float* lse, uint64_t ldl, std::string& why) {
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    const uint32_t w = heads * d;
+    if (int rc = hsw::check_features("q", q, ldq, w, why)) return rc;
+    if (int rc = hsw::check_features("k", k, ldk, w, why)) return rc;
+    if (int rc = hsw::check_features("v", v, ldv, w, why)) return rc;
+    if (int rc = hsw::check_features("y", y, ldy, w, why)) return rc;
+    if (lse)
+        if (int rc = check_lse(lse, ldl, heads, why)) return rc;
+    if (int rc = hsat::check_scale(scale, why)) return rc;
+    return hsat::check_overlaps(q, hsat::reach(num_rows, ldq, w), k, hsat::reach(num_cols, ldk, w), v, hsat::reach(num_cols, ldv, w), y, hsat::reach(num_rows, ldy, w), lse,
+                                lse_reach(num_rows, ldl, heads), why);
+}
+
+// hsmh_forward's: ld = heads * d, ldl = heads, no alignment rule (both implementations copy or walk the arrays as they are)
+inline int check_forward_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, const float* q, const float* k, const float* v, uint32_t heads, uint32_t d, float scale,
+                              const float* y, const float* lse, std::string& why) {
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    if (!q || !k || !v || !y) {
+        why = "null argument";
+        return HS_ERR_BAD_ARG;
+    }
+    if (int rc = hsat::check_scale(scale, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4;
+    return hsat::check_overlaps(q, rb, k, cb, v, cb, y, rb, lse, uint64_t(num_rows) * heads * 4, why);
+}
+
+inline int check_backward_flag(bool backward, std::string& why) {
+    if (!backward) {
+        why = "the object was created without HSMH_BACKWARD";
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+// hsmh_backward_device's arguments
+inline int check_backward(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool backward, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v,
+                          uint64_t ldv, const float* gy, uint64_t ldgy, const float* lse, uint64_t ldl, uint32_t heads, uint32_t d, float scale, const float* gq, uint64_t ldgq,
+                          const float* gk, uint64_t ldgk, const float* gv, uint64_t ldgv, std::string& why) {
+    if (int rc = check_backward_flag(backward, why)) return rc;
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    const uint32_t w = heads * d;
+    if (int rc = hsw::check_features("q", q, ldq, w, why)) return rc;
+    if (int rc = hsw::check_features("k", k, ldk, w, why)) return rc;
+    if (int rc = hsw::check_features("v", v, ldv, w, why)) return rc;
+    if (int rc = hsw::check_features("gy", gy, ldgy, w, why)) return rc;
+    if (int rc = check_lse(lse, ldl, heads, why)) return rc;
+    if (int rc = hsw::check_features("gq", gq, ldgq, w, why)) return rc;
+    if (int rc = hsw::check_features("gk", gk, ldgk, w, why)) return rc;
+    if (int rc = hsw::check_features("gv", gv, ldgv, w, why)) return rc;
+    if (int rc = hsat::check_scale(scale, why)) return rc;
+    const hsab::Range in[5] = {{"q", q, hsat::reach(num_rows, ldq, w)}, {"k", k, hsat::reach(num_cols, ldk, w)}, {"v", v, hsat::reach(num_cols, ldv, w)},
+                               {"gy", gy, hsat::reach(num_rows, ldgy, w)}, {"lse", lse, lse_reach(num_rows, ldl, heads)}};
+    const hsab::Range out[3] = {{"gq", gq, hsat::reach(num_rows, ldgq, w)}, {"gk", gk, hsat::reach(num_cols, ldgk, w)}, {"gv", gv, hsat::reach(num_cols, ldgv, w)}};
+    return hsab::check_overlaps(in, out, why);
+}
+
+// hsmh_backward's: ld = heads * d, ldl = heads, no alignment rule
+inline int check_backward_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool backward, const float* q, const float* k, const float* v, const float* gy,
+                               const float* lse, uint32_t heads, uint32_t d, float scale, const float* gq, const float* gk, const float* gv, std::string& why) {
+    if (int rc = check_backward_flag(backward, why)) return rc;
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    if (!q || !k || !v || !gy || !lse || !gq || !gk || !gv) {
+        why = "null argument";
+        return HS_ERR_BAD_ARG;
+    }
+    if (int rc = hsat::check_scale(scale, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4;
+    const hsab::Range in[5] = {{"q", q, rb}, {"k", k, cb}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, uint64_t(num_rows) * heads * 4}};
+    const hsab::Range out[3] = {{"gq", gq, rb}, {"gk", gk, cb}, {"gv", gv, cb}};
+    return hsab::check_overlaps(in, out, why);
+}
+
+}  // namespace hsmh
+}  // namespace hisparse
+
+#endif  // HISPARSE_HSMH_COMMON_H_

@@ -1,0 +1,229 @@
+// hsmh_cpu.cpp — include/hisparse_heads.h in libhisparse_cpu.so: multi-head attention over a CSR pattern, forward and backward, on the
+// host, for machines WITHOUT a GPU.  Like hsat_cpu.cpp and hsab_cpu.cpp a second implementation that a driver loads INSTEAD of
+// libhisparse_hip.so, never a fallback of it.  "Device" pointers are host pointers here, hsmh_set_stream accepts and ignores, hsmh_sync
+// is a no-op.  Single-threaded: plain loops on the calling thread, head by head, two passes per row (forward: the scores and their
+// maximum, then the weights and the sums; backward: the weights, the dots of gY and V and their sum D, then the three gradients); gK and
+// gV of a head are summed in double over all rows and rounded at the end.  HSMH_BACKWARD is recorded and checked as the device library
+// checks it; nothing is built for it.
+//
+// Arithmetic = the kernels' (heads_attention.hip), the header's ARITHMETIC paragraph: one fp32 multiply per product (built with
+// -ffp-contract=off), added in double, s rounded once; t = scale * s in fp32; everything after that in double, one rounding per output
+// word.
+// No dependency beyond the headers and hsmh_common.h: tests/cpp/test_heads_cpu.cpp compiles this file alone under the sanitizers.
+#include <cmath>
+#include <limits>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "hsmh_common.h"
+
+struct hsmh_pattern {
+    uint32_t num_rows = 0, num_cols = 0, max_heads = 0;
+    bool backward = false;
+    std::vector<uint32_t> indptr, indices;
+    std::string error;
+    uint64_t nnz() const { return indptr.back(); }
+};
+
+namespace {
+
+thread_local std::string g_create_error;
+
+int fail(hsmh_pattern* p, int code, const std::string& msg) {
+    if (p) p->error = msg; else g_create_error = msg;
+    return code;
+}
+
+// one head: the pointers are the head's first word of row 0, lse (may be null) its word of row 0
+void forward_head(const hsmh_pattern* p, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, uint32_t d, float scale, float* y, uint64_t ldy,
+                  float* lse, uint64_t ldl) {
+    const float ninf = -std::numeric_limits<float>::infinity();
+    std::vector<float> t;
+    std::vector<double> acc(d);
+    for (uint32_t r = 0; r < p->num_rows; ++r) {
+        const uint64_t lo = p->indptr[r], hi = p->indptr[r + 1];
+        float* dst = y + uint64_t(r) * ldy;
+        if (lo == hi) {
+            for (uint32_t j = 0; j < d; ++j) dst[j] = 0.0f;
+            if (lse) lse[uint64_t(r) * ldl] = ninf;
+            continue;
+        }
+        const float* a = q + uint64_t(r) * ldq;
+        t.resize(hi - lo);
+        float m = ninf;      // one of the t words; a NaN is never the maximum
+        for (uint64_t e = lo; e < hi; ++e) {
+            const float* b = k + uint64_t(p->indices[e]) * ldk;
+            double s = 0.0;
+            for (uint32_t j = 0; j < d; ++j) s += double(a[j] * b[j]);
+            t[e - lo] = scale * float(s);
+            m = std::fmax(m, t[e - lo]);
+        }
+        double l = 0.0;
+        acc.assign(d, 0.0);
+        for (uint64_t e = lo; e < hi; ++e) {
+            // a -inf score weighs exactly 0, also while the maximum is -inf itself; a NaN, or +inf under a maximum of +inf, gives NaN
+            const double w = t[e - lo] == ninf ? 0.0 : std::exp(double(t[e - lo]) - double(m));
+            const float* b = v + uint64_t(p->indices[e]) * ldv;
+            l += w;
+            for (uint32_t j = 0; j < d; ++j) acc[j] += w * double(b[j]);
+        }
+        for (uint32_t j = 0; j < d; ++j) dst[j] = float(acc[j] / l);
+        if (lse) lse[uint64_t(r) * ldl] = float(double(m) + std::log(l));
+    }
+}
+
+void backward_head(const hsmh_pattern* p, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, const float* gy, uint64_t ldgy, const float* lse,
+                   uint64_t ldl, uint32_t d, float scale, float* gq, uint64_t ldgq, float* gk, uint64_t ldgk, float* gv, uint64_t ldgv) {
+    std::vector<double> w, gp, row(d);
+    std::vector<double> sum_k(size_t(p->num_cols) * d, 0.0), sum_v(size_t(p->num_cols) * d, 0.0);
+    for (uint32_t r = 0; r < p->num_rows; ++r) {
+        const uint64_t lo = p->indptr[r], hi = p->indptr[r + 1];
+        float* dst = gq + uint64_t(r) * ldgq;
+        if (lo == hi) {
+            for (uint32_t j = 0; j < d; ++j) dst[j] = 0.0f;
+            continue;
+        }
+        const float* a = q + uint64_t(r) * ldq;
+        const float* g = gy + uint64_t(r) * ldgy;
+        // a word that is not finite (a dead or bad row of the forward) makes every weight of the row's head NaN
+        const float lw = lse[uint64_t(r) * ldl];
+        const double l = std::isfinite(lw) ? double(lw) : std::numeric_limits<double>::quiet_NaN();
+        w.resize(hi - lo);
+        gp.resize(hi - lo);
+        double dsum = 0.0;
+        for (uint64_t e = lo; e < hi; ++e) {
+            const float* b = k + uint64_t(p->indices[e]) * ldk;
+            const float* c = v + uint64_t(p->indices[e]) * ldv;
+            double s = 0.0, x = 0.0;
+            for (uint32_t j = 0; j < d; ++j) s += double(a[j] * b[j]);
+            for (uint32_t j = 0; j < d; ++j) x += double(g[j] * c[j]);
+            w[e - lo] = std::exp(double(scale * float(s)) - l);      // a -inf score under a finite lse weighs exactly 0
+            gp[e - lo] = x;
+            dsum += w[e - lo] * x;
+        }
+        row.assign(d, 0.0);
+        for (uint64_t e = lo; e < hi; ++e) {
+            const uint32_t c = p->indices[e];
+            const double pe = w[e - lo], gs = double(scale) * (pe * (gp[e - lo] - dsum));
+            const float* b = k + uint64_t(c) * ldk;
+            double* to_k = sum_k.data() + size_t(c) * d;
+            double* to_v = sum_v.data() + size_t(c) * d;
+            for (uint32_t j = 0; j < d; ++j) {
+                row[j] += gs * double(b[j]);
+                to_k[j] += gs * double(a[j]);
+                to_v[j] += pe * double(g[j]);
+            }
+        }
+        for (uint32_t j = 0; j < d; ++j) dst[j] = float(row[j]);
+    }
+    for (uint32_t c = 0; c < p->num_cols; ++c) {
+        for (uint32_t j = 0; j < d; ++j) {
+            gk[uint64_t(c) * ldgk + j] = float(sum_k[size_t(c) * d + j]);
+            gv[uint64_t(c) * ldgv + j] = float(sum_v[size_t(c) * d + j]);
+        }
+    }
+}
+
+void forward(const hsmh_pattern* p, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, uint32_t heads, uint32_t d, float scale, float* y,
+             uint64_t ldy, float* lse, uint64_t ldl) {
+    for (uint32_t h = 0; h < heads; ++h) {
+        const uint32_t at = h * d;
+        forward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, d, scale, y + at, ldy, lse ? lse + h : nullptr, ldl);
+    }
+}
+
+void backward(const hsmh_pattern* p, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, const float* gy, uint64_t ldgy, const float* lse,
+              uint64_t ldl, uint32_t heads, uint32_t d, float scale, float* gq, uint64_t ldgq, float* gk, uint64_t ldgk, float* gv, uint64_t ldgv) {
+    for (uint32_t h = 0; h < heads; ++h) {
+        const uint32_t at = h * d;
+        backward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, gy + at, ldgy, lse + h, ldl, d, scale, gq + at, ldgq, gk + at, ldgk, gv + at, ldgv);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int hsmh_create(hsmh_pattern** out, int device_id, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, uint32_t max_heads, uint32_t flags) {
+    (void)device_id;
+    if (!out) return fail(nullptr, HS_ERR_BAD_ARG, "null pattern pointer");
+    *out = nullptr;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_create(num_rows, num_cols, indptr, indices, max_heads, flags, why)) return fail(nullptr, rc, why);
+    hsmh_pattern* p = new (std::nothrow) hsmh_pattern;
+    if (!p) return fail(nullptr, HS_ERR_NO_MEMORY, "out of memory");
+    p->num_rows = num_rows;
+    p->num_cols = num_cols;
+    p->max_heads = max_heads;
+    p->backward = (flags & HSMH_BACKWARD) != 0;
+    p->indptr.assign(indptr, indptr + size_t(num_rows) + 1);
+    if (p->nnz()) p->indices.assign(indices, indices + p->nnz());
+    *out = p;
+    return HS_OK;
+}
+
+int hsmh_destroy(hsmh_pattern* p) {
+    delete p;
+    return HS_OK;
+}
+
+const char* hsmh_last_error(const hsmh_pattern* p) { return p ? p->error.c_str() : g_create_error.c_str(); }
+
+int hsmh_info(const hsmh_pattern* p, uint64_t* nnz, uint64_t* device_bytes) {
+    if (!p) return HS_ERR_BAD_ARG;
+    if (nnz) *nnz = p->nnz();
+    if (device_bytes) *device_bytes = 0;      // nothing lives on a device
+    return HS_OK;
+}
+
+int hsmh_set_stream(hsmh_pattern* p, void* hip_stream) {
+    (void)hip_stream;
+    return p ? HS_OK : HS_ERR_BAD_ARG;
+}
+
+int hsmh_sync(hsmh_pattern* p) { return p ? HS_OK : HS_ERR_BAD_ARG; }
+
+int hsmh_forward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, uint32_t heads, uint32_t d, float scale,
+                        float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward(p->num_rows, p->num_cols, p->max_heads, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    forward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl);
+    return HS_OK;
+}
+
+// the host forms: ld = heads * d, ldl = heads and no alignment rule, so the loops walk the caller's arrays as they are
+int hsmh_forward(hsmh_pattern* p, const float* q, const float* k, const float* v, uint32_t heads, uint32_t d, float scale, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_host(p->num_rows, p->num_cols, p->max_heads, q, k, v, heads, d, scale, y, lse, why)) return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    forward(p, q, w, k, w, v, w, heads, d, scale, y, w, lse, heads);
+    return HS_OK;
+}
+
+int hsmh_backward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* gy_dev, uint64_t ldgy,
+                         const float* lse_dev, uint64_t ldl, uint32_t heads, uint32_t d, float scale, float* gq_dev, uint64_t ldgq, float* gk_dev, uint64_t ldgk, float* gv_dev,
+                         uint64_t ldgv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward(p->num_rows, p->num_cols, p->max_heads, p->backward, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale,
+                                                gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, why))
+        return fail(p, rc, why);
+    backward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv);
+    return HS_OK;
+}
+
+int hsmh_backward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* gy, const float* lse, uint32_t heads, uint32_t d, float scale, float* gq, float* gk,
+                  float* gv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_host(p->num_rows, p->num_cols, p->max_heads, p->backward, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    backward(p, q, w, k, w, v, w, gy, w, lse, heads, heads, d, scale, gq, w, gk, w, gv, w);
+    return HS_OK;
+}
+
+}  // extern "C"
