@@ -28,11 +28,45 @@ const char* const kOptionKeys[] = {
     "VALUE_MAP",
 };
 
-hisparse::dev::SpmvLaunch launch_args(const hs_context* c, const uint32_t* x, uint32_t* y, int32_t filter) {
+static_assert(hisparse::dev::kRowblockResidentMaxImageBytes == hisparse::dev::kResidentMaxImageBytes, "one cache, one budget for the reuse tracker");
+
+// The stream cache policy of ONE launch (reuse_tracker.h): `sc1` when the caller's option says so, or when no option is set, the image's shape is
+// eligible and the device's tracker finds it warm -- the images launched since its previous launch, itself included, streamed no more than the
+// Infinity Cache holds.  Every launch is recorded, of every format and under either policy; a row partition counts as its whole image (its bytes
+// were last read one partition loop ago).  While the stream is capturing, nothing executes: the decision is taken on a copy of the tracker's state
+// -- this context's own captures keep one copy from step to step, so a captured batch from a cold state is `nt` for step 1 and resident for the
+// rest, and touch the tracker once per replay (replayed); a caller's capture of a stream it owns, whose replays the library does not see, decides
+// each launch on a fresh copy.
+bool launch_stream_resident(hs_context* c) {
+    const MatrixData& m = c->mat;
+    const uint64_t budget = hisparse::dev::kResidentMaxImageBytes;
+    if (c->capturing) return hisparse::launch_resident(c->capture_list, m.resident_forced, m.resident_eligible, m.image_id, m.image_bytes, budget);
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (c->stream != c->own_stream && hipStreamIsCapturing(c->stream, &capture) == hipSuccess && capture != hipStreamCaptureStatusNone) {
+        hisparse::ReuseList copy = c->reuse->snapshot();
+        return hisparse::launch_resident(copy, m.resident_forced, m.resident_eligible, m.image_id, m.image_bytes, budget);
+    }
+    return c->reuse->launch_resident(m.resident_forced, m.resident_eligible, m.image_id, m.image_bytes, budget);
+}
+
+// This context captures its own launches from here to the end of the scope
+struct CaptureScope {
+    hs_context* c;
+    explicit CaptureScope(hs_context* ctx) : c(ctx) {
+        c->capture_list = c->reuse->snapshot();
+        c->capturing = true;
+    }
+    ~CaptureScope() { c->capturing = false; }
+};
+// one replay of a captured graph ran the loaded image
+void replayed(hs_context* c) { c->reuse->touch(c->mat.image_id, c->mat.image_bytes); }
+
+hisparse::dev::SpmvLaunch launch_args(hs_context* c, const uint32_t* x, uint32_t* y, int32_t filter) {
     hisparse::dev::SpmvLaunch a = c->mat.launch;
     a.x = x;
     a.out = c->mat.col_slices > 1 ? c->carry.partial() : y;
     a.row_part_filter = filter;
+    a.stream_resident = launch_stream_resident(c);
     return a;
 }
 
@@ -201,6 +235,7 @@ int hs_create(hs_context** out, int device_id, int impl, uint32_t ob_bank, uint3
     hs_context* c = new (std::nothrow) hs_context;
     if (!c) return fail(nullptr, HS_ERR_NO_MEMORY, "out of memory");
     c->device = device_id;
+    c->reuse = &hisparse::reuse_tracker_for(device_id);
     c->impl = impl;
     c->geom = hisparse::make_geometry(impl, ob_bank ? ob_bank : hisparse::impl_default_ob_bank(impl),
                                       vb_bank ? vb_bank : hisparse::impl_default_vb_bank(impl));
@@ -304,7 +339,10 @@ int hs_run_batch(hs_context* ctx, uint32_t steps) {
         if ((rc = ::settle(ctx)) != HS_OK) return rc;        // the graph owes nothing when it begins ...
         hipError_t e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
         if (e != hipSuccess) return hip_fail(ctx, e, "hipStreamBeginCapture (the legacy default stream cannot be captured)");
-        for (uint32_t i = 0; i < steps && rc == HS_OK; ++i) rc = step(ctx);
+        {
+            CaptureScope capture(ctx);                       // the steps' cache policies are decided on a copy of the reuse tracker and frozen
+            for (uint32_t i = 0; i < steps && rc == HS_OK; ++i) rc = step(ctx);
+        }
         if (rc == HS_OK) rc = ::settle(ctx);                 // ... and nothing when it ends (a carried plan: K kernels + one combine)
         e = hipStreamEndCapture(ctx->stream, &ctx->batch_graph);
         if (rc == HS_OK && (e != hipSuccess || !ctx->batch_graph)) rc = hip_fail(ctx, e, "hipStreamEndCapture");
@@ -323,6 +361,7 @@ int hs_run_batch(hs_context* ctx, uint32_t steps) {
     }
     if ((rc = ::settle(ctx)) != HS_OK) return rc;
     HS_HIP(ctx, hipGraphLaunch(ctx->batch_exec, ctx->stream));
+    replayed(ctx);
     return HS_OK;
 }
 
@@ -360,11 +399,17 @@ int hs_iterate(hs_context* ctx, uint32_t iterations, uint32_t scale_word, uint32
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     if (chunk > 1 && hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        for (uint32_t i = 0; i < chunk && rc == HS_OK; ++i) rc = one_iteration();
+        {
+            CaptureScope capture(ctx);
+            for (uint32_t i = 0; i < chunk && rc == HS_OK; ++i) rc = one_iteration();
+        }
         const hipError_t end = hipStreamEndCapture(ctx->stream, &graph);
         if (rc == HS_OK && end == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
             hipError_t e = hipSuccess;
-            for (; done + chunk <= iterations && e == hipSuccess; done += chunk) e = hipGraphLaunch(exec, ctx->stream);
+            for (; done + chunk <= iterations && e == hipSuccess; done += chunk) {
+                e = hipGraphLaunch(exec, ctx->stream);
+                replayed(ctx);
+            }
             (void)hipGraphExecDestroy(exec);
             (void)hipGraphDestroy(graph);
             if (e != hipSuccess) return fail(ctx, HS_ERR_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(e));
@@ -525,11 +570,11 @@ int hs_time_kernel(hs_context* ctx, int warmup, int runs, float* kernel_ms) {
     if (warmup < 0 || runs <= 0 || !kernel_ms) return fail(ctx, HS_ERR_BAD_ARG, "need warmup >= 0, runs > 0 and an output pointer");
     if (const char* why = hisparse::dev::profiling_switch_error()) return fail(ctx, HS_ERR_BAD_ARG, why);
     if ((rc = enter(ctx, 0)) != HS_OK) return rc;
-    const hisparse::dev::SpmvLaunch args = launch_args(ctx, ctx->x_source(), ctx->y_target(), -1);
     // a plan whose combine pass is carried into the next step's kernel: the kernel as it runs in consecutive steps, i.e. with that work in it
     const bool carried = ctx->carry.carries() && ctx->stream_private();
     auto launch = [&]() -> int {
         if (carried) return step(ctx);
+        const hisparse::dev::SpmvLaunch args = launch_args(ctx, ctx->x_source(), ctx->y_target(), -1);      // (per launch: its cache policy is the launch's)
         HS_HIP(ctx, hisparse::dev::launch_spmv(ctx->is_float(), args, ctx->stream));
         return HS_OK;
     };

@@ -19,6 +19,7 @@
 
 #include "device_buffer.h"      // DeviceBuffer, PinnedBuffer, DeviceEvent: the owners of device memory, pinned memory, events
 #include "hisparse/common.h"
+#include "reuse_tracker.h"
 #include "spmv_kernels.h"
 #include "stream_tiles.h"
 #include "tiles_common.h"
@@ -110,7 +111,14 @@ struct MatrixData {
     DeviceBuffer<hisparse::dev::Block> blocks;
     DeviceBuffer<hisparse::dev::Unit> units;
     DeviceBuffer<uint32_t> part_heads;
-    hisparse::dev::SpmvLaunch launch{};   // the plan as launch_spmv takes it (the pointers above, format, LDS bytes, ...): a step adds x, out and its row-partition filter
+    hisparse::dev::SpmvLaunch launch{};   // the plan as launch_spmv takes it (the pointers above, format, LDS bytes, ...): a step adds x, out, its row-partition filter
+                                          // and its stream cache policy (below)
+    // The stream cache policy is a launch's, not the load's (hs_api.cpp: launch_args; reuse_tracker.h): what the device's tracker knows this image by --
+    // an id no other load has had, fresh again after hs_update_values -- and what the load contributes: the caller's stream_resident option (0 | 1;
+    // -1: none) and whether the image's shape may be streamed resident at all (stream_tiles.h: plan_stream_resident).
+    uint64_t image_id = 0, image_bytes = 0;
+    int resident_forced = -1;
+    bool resident_eligible = false;
     uint32_t col_slices = 1;
     bool crossing_blocks = false;   // some row block reaches over a row-partition border (tiles_common.h: Layout::cross_parts)
     uint32_t max_block_rows = 0;
@@ -185,6 +193,12 @@ struct hs_context {
     const void* batch_x = nullptr;
     void* batch_y = nullptr;
     hipStream_t batch_stream = nullptr;
+
+    // The device's reuse tracker (one per device, shared by its contexts), and the copy of its state that launches decide on while this context
+    // captures its stream (hs_run_batch with batch_graph, hs_iterate with iterate_graph): captured launches execute later, once per replay
+    hisparse::ReuseTracker* reuse = nullptr;
+    hisparse::ReuseList capture_list;
+    bool capturing = false;
 
     bool vector_loaded = false;
     DeviceBuffer<uint32_t> d_x;    // library-owned packed x

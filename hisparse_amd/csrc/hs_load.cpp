@@ -151,8 +151,12 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
     // the two decisions of stream_tiles.h, unless an option decides otherwise
     const uint64_t image_bytes = image_on_device ? tiles.image_bytes : uint64_t(tiles.image.size());
     const char* resident_opt = ctx_option(ctx, "HISPARSE_STREAM_RESIDENT");
-    m.launch.stream_resident = resident_opt ? std::atoi(resident_opt) != 0
-                                     : hisparse::dev::plan_stream_resident(tiles.format, tiles.light, image_bytes, tiles.units.size(), tiles.blocks.size(), tiles.value_bits);
+    // (stream residency: the load says whether the image MAY be streamed resident; each launch decides whether it is: hs_api.cpp, launch_args)
+    m.resident_forced = resident_opt ? int(std::atoi(resident_opt) != 0) : -1;
+    m.resident_eligible = hisparse::dev::stream_policy_applies(tiles.format, tiles.light) &&
+                          hisparse::dev::plan_stream_resident(tiles.format, tiles.light, image_bytes, tiles.units.size(), tiles.blocks.size());
+    m.image_id = hisparse::next_image_id();
+    m.image_bytes = image_bytes;
     const char* carry_opt = ctx_option(ctx, "HISPARSE_CARRY_COMBINE");
     // (a packed DELTA image is judged by the size of its plain form here too: packing changes the bytes of a step, not which of the two regimes it is in)
     const uint64_t carry_bytes = tiles.format == hisparse::dev::kFormatDelta && tiles.value_bits == 24
@@ -237,7 +241,7 @@ int load_matrix_once(hs_context* ctx, const void* const* channel, const uint64_t
     s.retiled_on_gpu = image_on_device;
     s.light_kernel = tiles.light ? 1u : 0u;
     s.value_bits = tiles.value_bits;
-    s.stream_resident = a.stream_resident && hisparse::dev::stream_policy_applies(tiles.format, tiles.light) ? 1u : 0u;
+    s.stream_resident = (m.resident_forced >= 0 ? m.resident_forced != 0 : m.resident_eligible) && hisparse::dev::stream_policy_applies(tiles.format, tiles.light) ? 1u : 0u;
     return HS_OK;
 }
 
@@ -328,6 +332,7 @@ int update_values(hs_context* ctx, const float* values, uint64_t nnz, bool from_
     HS_HIP(ctx, hisparse::dev::launch_value_update(ctx->impl == HS_IMPL_FIXED, src, nnz, m.value_map.get(), reinterpret_cast<uint32_t*>(m.image.get()),
                                                    ctx->stats.stream_bytes / 4, m.mfma.value_map.get(), m.mfma.words.get(), m.mfma.value_map ? m.mfma.info.words_bytes / 4 : 0,
                                                    uint32_t(ctx->compute_units), ctx->stream));
+    m.image_id = hisparse::next_image_id();      // the image was rewritten: cold to the device's reuse tracker, like a reload
     if (from_host) HS_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the caller may reuse `values` immediately (as after hs_load_vector)
     return HS_OK;
 }

@@ -31,7 +31,8 @@ struct SpmvLaunch {
     const uint32_t* carry_partial = nullptr;
     uint32_t* carry_y = nullptr;
     uint32_t carry_rows = 0, carry_slices = 0;
-    bool stream_resident = false; // the image is small enough to stay in the 256 MiB Infinity Cache from one step to the next: SWEEP stream loads WITHOUT the non-temporal hint (spmv_sweep.hip)
+    bool stream_resident = false; // this launch finds the image in the 256 MiB Infinity Cache and leaves it there: SWEEP / PAIRS / DELTA stream loads WITHOUT the non-temporal hint
+                                  // (spmv_sweep.hip, spmv_kernels.hip).  Set per launch (hs_api.cpp: launch_args), not by the load
     bool light = false;           // the LIGHT plan (StreamTiles::light): a PAIRS image consumed by spmv_light_kernel, 256-thread workgroups, lds_bytes = spmv_light_lds_bytes
 };
 

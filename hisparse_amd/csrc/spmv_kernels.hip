@@ -106,7 +106,7 @@ __device__ __forceinline__ void dma_wait() {
 //     refill at every unit border -- ogbl-ppa's 8-way slabs 16.8 -> 15.3 us, its 2-way slabs 34.8 -> 32.1, mouse_gene 33.8 -> 33.4, the sliced DELTA
 //     plans of the pruned-NN layers -2.5 % -- while a pure stream keeps `nt`: hollywood (872 MB) 137.5 -> 155 us without it, ogbn-products 203 -> 208, the
 //     headline matrix round-robin over three images 56 -> 65 us, and the one-unit-per-block slabs of mouse_gene 12.4 -> 12.9 / 20.0 -> 20.9
-//     (profiles/r06_rowblock_stream_policy*.txt).  A plan-time choice (stream_tiles.h: plan_stream_resident), a template parameter here: bit 2 of kRing.
+//     (profiles/r06_rowblock_stream_policy*.txt).  A launch-time choice (hs_api.cpp: launch_args; eligibility: stream_tiles.h: plan_stream_resident), a template parameter here: bit 2 of kRing.
 #ifndef HS_ROWBLOCK_STREAM_POLICY
 #define HS_ROWBLOCK_STREAM_POLICY "nt"      // the stream loads of an image that is streamed from HBM every time
 #endif

@@ -98,11 +98,13 @@ constexpr uint32_t kMaxSweepSlices = 16;      // SWEEP images (round 5): a short
 // of hollywood split 8 ways (SWEEP, 113 MB) 24.6 -> 24.1, of ogbl-ppa split 2 ways (155 MB) 32.2 -> 31.4: carried up to 160 MiB.
 constexpr uint64_t kCarryMaxImageBytes = 160ull << 20;
 constexpr uint64_t kSlicedDeltaMaxImageBytes = 48ull << 20;   // the sliced DELTA plan of fixed-point dense layers (stream_plan.h: choose_dense_rows): measured up to 8.5 M non-zeros, no further
-constexpr uint64_t kResidentMaxImageBytes = 256ull << 20;   // SWEEP images up to the size of the Infinity Cache are streamed without the non-temporal hint (plan_stream_resident below)
-// Row-block (PAIRS / DELTA) images, round 6 (profiles/r06_rowblock_stream_policy*.txt): without `nt` where the image fits the Infinity Cache AND its blocks walk
-// several units.  Measured to gain a little even above the cache (ogbl-ppa, 267 MiB: -1.5 % warm) -- but an image that does not fit is evicted between
-// steps anyway, and once a caller alternates between matrices the cacheable policy COSTS: the headline matrix round-robin over three images ran 65.4 us per SpMV
-// with `sc1` streams against 56 us with `nt` (bench.py's MALL-cold leg), hollywood (872 MB) 155 against 137 us.  So: the cache's own size, no more.
+constexpr uint64_t kResidentMaxImageBytes = 256ull << 20;   // the Infinity Cache: SWEEP images up to its size MAY be streamed without the non-temporal hint (plan_stream_resident below), and
+                                                            // it is the byte budget of the launch-time reuse tracker (reuse_tracker.h)
+// Row-block (PAIRS / DELTA) images, round 6 (profiles/r06_rowblock_stream_policy*.txt): eligible for `sc1` streams where the image fits the Infinity Cache at all
+// AND its blocks walk several units.  Whether an eligible image IS in the cache is not a property of the image: a loop over one image gains 8-9 % from `sc1`
+// (one rank's slab of ogbl-ppa split 2 ways, 155 MB: 34.8 -> 32.1 us), while a caller that alternates between matrices PAYS for it -- the plain headline image
+// round-robin over three ran 65.4 us per SpMV with `sc1` streams against 56 us with `nt` (bench.py's MALL-cold leg), hollywood (872 MB) 155 against 137 us.  So this
+// constant is only the "fits the cache at all" clause; each launch takes the policy by the image's reuse distance (hs_api.cpp: launch_args).
 // One-unit-per-block plans (a pure stream per block, no drained pipeline to refill) keep `nt` unless the whole image is a few tens of MB, where the
 // step is launch- and latency-bound (the sliced DELTA plans of the pruned-NN layers: -2.5 %; mouse_gene's 50 / 100 MB slabs: +4 %).
 constexpr uint64_t kRowblockResidentMaxImageBytes = 256ull << 20;
@@ -156,26 +158,27 @@ constexpr uint64_t kDeltaMinSavedBytesFloat = 40u << 20;      // ... 6 us in the
 constexpr double kDenseMeanGap = 320.0;                       // DELTA blocks denser than this (>= 24 elements per row and sub-tile) sum per lane in registers (kBlockDenseRows);
                                                               // sparser ones lose with it (400000 x 100000, gap 512: 89.8 vs 83.2 us), denser ones win big (40000^2, gap 64: 34.5 vs 53.0)
 enum StreamFormat : uint32_t { kFormatPairs = 0, kFormatDelta = 1, kFormatBitmap = 2, kFormatOwner = 3, kFormatPairs24 = 4, kFormatOwner24 = 5, kFormatSweep = 6 };
-// The two plan-time decisions of a load that are not the planner's (hs_load.cpp; the options `stream_resident` / `carry_combine` = 0 | 1 decide otherwise).
+// The two decisions of a load that are not the planner's (hs_load.cpp; the options `stream_resident` / `carry_combine` = 0 | 1 decide otherwise).
 //
-// Stream residency.  SWEEP images that fit the 256 MiB Infinity Cache are streamed WITHOUT the non-temporal hint: repeated SpMVs of one matrix -- the
-// reference's benchmark loop, an iterative caller -- then read most of the image from the cache (profiles/r05_sweep_stream_policy.txt: one
-// rank's slab of ogbn-products split 8 ways, 124 MB: 39.5 -> 32.0 us; pokec, 247 MB: 61.1 -> 59.6-60.8 fixed, 69.3-70.3 -> 66.3-67.7 float_pob).
-// Larger images keep `nt` (a plain read loop over 1 GiB: 7.1 TB/s with it, 6.0 without: profiles/r02_hbm_read_bench.txt).
-// Round 6: the row-block kernels' PAIRS / DELTA streams too (spmv_kernels.hip: Ring<kRing | 4>), by their own rule (kRowblockResidentMaxImageBytes
-// above): up to the size of the cache where the blocks walk several units, tiny images whatever their shape; pure one-unit streams and everything
-// larger keep `nt` (hollywood: +13 % without it).  OWNER / OWNER24 / BITMAP / LIGHT images have no kernel without the hint: the decision is
-// taken for them by the SWEEP rule and has no effect (stream_policy_applies; hs_stats::stream_resident reports 0).
+// Stream residency.  The SWEEP kernels and the row-block kernels' PAIRS / DELTA streams (spmv_sweep.hip; spmv_kernels.hip: Ring<kRing | 4>) exist with and
+// WITHOUT the non-temporal hint on their stream loads.  Without it (`sc1`), repeated SpMVs of one matrix -- the reference's benchmark loop, an iterative
+// caller -- read most of the image from the 256 MiB Infinity Cache (profiles/r05_sweep_stream_policy.txt: one rank's slab of ogbn-products split 8 ways,
+// 124 MB: 39.5 -> 32.0 us; pokec, 247 MB: 61.1 -> 59.6-60.8 fixed; profiles/r06_rowblock_stream_policy_large.txt: 8-9 % on row-block slabs); with it (`nt`)
+// an image that will not be found in the cache anyway does not evict what would (a plain read loop over 1 GiB: 7.1 TB/s with it, 6.0 without:
+// profiles/r02_hbm_read_bench.txt; hollywood: +13 % without it).
+// The LOAD decides eligibility only, by shape (plan_stream_resident; hs_stats::stream_resident reports it: "may be streamed resident while warm"): SWEEP images
+// up to the size of the cache; row-block images up to that size where the blocks walk several units, tiny images whatever their shape; pure one-unit
+// streams and everything larger keep `nt`.  Every image is judged by its own bytes, a packed DELTA image too.  Each LAUNCH of an eligible image then takes
+// `sc1` when the device's reuse tracker finds the image warm -- the images launched since its previous launch, counted once each, plus itself streamed
+// no more than the cache holds -- and `nt` otherwise (hs_api.cpp: launch_args; reuse_tracker.h), so a loop over one image runs resident from its second
+// step and a round-robin over more than the cache runs `nt` throughout (profiles/launch_policy_ab.txt).  The option, 0 | 1, is always `nt` / always `sc1`.
+// OWNER / OWNER24 / BITMAP / LIGHT images have no kernel without the hint: never eligible (stream_policy_applies; hs_stats::stream_resident reports 0);
+// their launches are recorded by the tracker like any other.
 constexpr bool rowblock_stream(uint32_t format, bool light) { return (format == kFormatPairs || format == kFormatDelta) && !light; }
 constexpr bool stream_policy_applies(uint32_t format, bool light) { return format == kFormatSweep || rowblock_stream(format, light); }
-// A packed DELTA image (value_bits == 24) is judged by the size of its PLAIN form, so that packing by itself never flips the policy: ogbl-ppa's
-// image shrinks from 267 to 222.5 MiB, under the cache's size, and would silently go from `nt` to `sc1` -- which on this matrix gained 1.5 % warm
-// and cost 14 % in the round-robin leg (above).  The rule: `nt` stays unless `sc1` wins both legs.  On the packed image only the warm leg was measured
-// (profiles/delta24_ab.txt: `sc1` -4.1 us of kernel time); its round-robin leg is unmeasured, so `nt` stays.
-constexpr bool plan_stream_resident(uint32_t format, bool light, uint64_t image_bytes, uint64_t num_units, uint64_t num_blocks, uint32_t value_bits = 0) {
-    const uint64_t judged_bytes = format == kFormatDelta && value_bits == 24 ? image_bytes / kRecordBytes24 * kRecordBytes : image_bytes;
+constexpr bool plan_stream_resident(uint32_t format, bool light, uint64_t image_bytes, uint64_t num_units, uint64_t num_blocks) {
     return rowblock_stream(format, light)
-               ? judged_bytes <= kRowblockResidentMaxImageBytes && (num_units > num_blocks || judged_bytes <= kRowblockResidentSmallImageBytes)
+               ? image_bytes <= kRowblockResidentMaxImageBytes && (num_units > num_blocks || image_bytes <= kRowblockResidentSmallImageBytes)
                : image_bytes <= kResidentMaxImageBytes;
 }
 // The combine pass carried into the next step's kernel (hs_context.h: CarriedCombine), for plans of several column slices.

@@ -79,7 +79,7 @@ typedef struct {
     double load_seconds;        /* wall time of the last hs_load_matrix (decode + re-tile + H2D) */
     uint32_t retiled_on_gpu;    /* 1: the per-non-zero passes of the re-tiling ran on the device (gpu_tiles.h); 0: on the host */
     uint32_t light_kernel;      /* 1: the LIGHT plan -- a small matrix run by the 256-thread single-launch kernel (spmv_light_kernel) over a PAIRS image */
-    uint32_t stream_resident;   /* 1: the plan found the image resident in the 256 MiB Infinity Cache across consecutive SpMVs and streams it WITHOUT the non-temporal hint (SWEEP images up to the cache size; PAIRS / DELTA images by the rule of stream_tiles.h: kRowblockResidentMaxImageBytes); option "stream_resident" = 0 | 1 decides otherwise */
+    uint32_t stream_resident;   /* 1: the image may be streamed resident while warm -- its shape is eligible (SWEEP images up to the 256 MiB Infinity Cache; PAIRS / DELTA images by the rule of stream_tiles.h: kRowblockResidentMaxImageBytes, every image judged by its own bytes), and each launch then streams it WITHOUT the non-temporal hint when the images launched on the device since its previous launch, itself included, add up to no more than the cache (reuse_tracker.h), with the hint otherwise; option "stream_resident" = 0 | 1 decides otherwise: every launch with / without the hint */
     uint32_t value_bits;        /* HS_STREAM_DELTA images: 24 = value words packed into 24-bit fields (640-byte records, a shift per image, outliers in per-block lists: stream_tiles.h) or 32 = plain value words (768-byte records); 0 for every other format */
 } hs_stats;
 
@@ -177,7 +177,7 @@ int hs_push_result(hs_context* ctx, void* const* dst, uint32_t n_dst, uint32_t n
  * (pairs|delta|delta24|delta32|owner|owner24|sweep|bitmap; delta: DELTA whose value words are packed into 24-bit fields when that saves 23 MiB of image, delta24: packed wherever the matrix allows it -- fixed point, no value map, at most one outlier per 4096 slots --, delta32: never packed; hs_stats.value_bits says which), col_slices, max_rows, cross_partitions (0: row blocks end at the reference's row-partition borders), spmm_vectors (4: plan the image for the four-column SpMM kernel, see hs_spmm), row_runs, delta_deal (wave: the dealing of DELTA runs of rounds 1-4), pow2_slices (1: column-slice counts 1, 2, 4, 8 only for matrices of more than sixteen sub-tiles, the rule of rounds 1-4), aux_bits, xcd_affinity, retile (host), bitmap_skew, bitmap_x_lds,
  * bitmap_build, walk_lanes, no_mfma_image, mfma_chunk (1 ... 65536 groups per wavefront unit of the matrix engine's image; a unit of all the groups of a row or more is the whole row; anything else is HS_ERR_BAD_ARG here, or from the load when it comes from the environment), light (0|1: the small-matrix kernel), sweep (0|1: the
  * column-ordered format of very sparse matrices), plan_debug; call-time keys: spmm_fused, spmm_mfma,
- * spmspv (sparse|auto|dense), spmspv_crossover, iterate_graph, batch_graph (hs_run_batch); carry_combine (0|1, plan-time: see hs_run), stream_resident (0|1, plan-time: SWEEP and PAIRS / DELTA images streamed without the non-temporal hint; default: SWEEP images up to 256 MiB, the Infinity Cache; PAIRS / DELTA images up to 256 MiB whose blocks walk several units, or up to 32 MiB: hs_stats.stream_resident says what the plan took).  autotune (0|1, plan-time, round 6: the load builds the planner's own image AND every other element format the matrix can take, times a few SpMVs of each on a zero vector and keeps the fastest -- a handful of extra loads of tens of milliseconds each, for callers that run one matrix thousands of times; a forced stream_format switches it off; hs_get_stats says what was kept), plan_census (0: plan from the rows' non-zero counts alone, as rounds 1-5 did), value_map (0|1, plan-time: hs_load_matrix_csr keeps the value map of hs_update_values).  value NULL or "" clears the option.  An unknown key is HS_ERR_BAD_ARG.
+ * spmspv (sparse|auto|dense), spmspv_crossover, iterate_graph, batch_graph (hs_run_batch); carry_combine (0|1, plan-time: see hs_run), stream_resident (0|1, plan-time: SWEEP and PAIRS / DELTA images streamed with | without the non-temporal hint at every launch; default: decided per launch -- SWEEP images up to 256 MiB, the Infinity Cache, and PAIRS / DELTA images up to 256 MiB whose blocks walk several units, or up to 32 MiB, are eligible (hs_stats.stream_resident says so), and an eligible image is streamed without the hint while it is warm: while the images launched on its device since its previous launch, itself included, add up to no more than the cache).  autotune (0|1, plan-time, round 6: the load builds the planner's own image AND every other element format the matrix can take, times a few SpMVs of each on a zero vector and keeps the fastest -- a handful of extra loads of tens of milliseconds each, for callers that run one matrix thousands of times; a forced stream_format switches it off; hs_get_stats says what was kept), plan_census (0: plan from the rows' non-zero counts alone, as rounds 1-5 did), value_map (0|1, plan-time: hs_load_matrix_csr keeps the value map of hs_update_values).  value NULL or "" clears the option.  An unknown key is HS_ERR_BAD_ARG.
  * Options set here win over the environment variable of the same name, which stays as the fallback for tools and tests.  None of them
  * changes WHAT is computed.  The switches that do (HISPARSE_ABLATE, HISPARSE_DEPTH: profiling builds with parts of the work removed) are
  * not options: they exist only in libhisparse_hip_prof.so, and this library refuses to run (HS_ERR_BAD_ARG from hs_run, hs_run_partition,

@@ -73,6 +73,11 @@ def model(name, cp=None, impl=None):
     packed = t["format"] == "owner24"
     es = (units["end_step"] & 0xFFFF if packed else units["end_step"]).astype(np.int64)
     step_bytes = {"pairs": 512, "pairs24": 448, "delta": 768, "owner": 512, "owner24": 448}[t["format"]]      # per wavefront step (DELTA: a record of two slots per lane)
+    if t["format"] == "delta" and t.get("value_bits") == 24:
+        # the packed record (stream_tiles.h: kRecordBytes24).  Refitted with the launch-time stream cache policy: the model had kept the plain record's 768
+        # bytes for packed images, 55 us for ogbl-ppa where its `nt` kernel ran 48-50 us -- inside the test's 15 % -- and the warm loop now runs `sc1` at
+        # 42-44 us (profiles/launch_policy_ab.txt).  With the bytes the image really has: ogbl-ppa 47.3, mouse_gene 34.2, the R-MAT stand-in 48.7 us
+        step_bytes = 640
     rate, floor = CU_STREAM_B_PER_US[family], UNIT_FLOOR_US[family]
     main = np.zeros(groups); stream = np.zeros(groups); floors = np.zeros(groups); nblocks = np.zeros(groups); elems = np.zeros(groups)
     for g in range(groups):
