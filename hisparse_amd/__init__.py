@@ -8,6 +8,7 @@ Layout:
   attention.py ctypes face of include/hisparse_attention.h (scores, row softmax and weighted sum over a CSR pattern in one call)
   attention_backward.py ctypes face of include/hisparse_attention_backward.h (the backward of that step, from lse to gQ, gK and gV)
   heads.py     ctypes face of include/hisparse_heads.h (multi-head attention over a CSR pattern, forward and backward, all heads per call)
+  heads16.py   ctypes face of include/hisparse_heads_bf16.h (the same object with bf16 operands)
   datasets.py  the reference's benchmark matrices as seeded stand-ins
   sharding.py  row-block sharding of one matrix across the GPUs of a node (+ RCCL gather of y)
   csrc/        C++ / HIP sources of the two libraries and the `benchmark` driver
@@ -20,5 +21,6 @@ from . import wide  # noqa: F401
 from . import attention  # noqa: F401
 from . import attention_backward  # noqa: F401
 from . import heads  # noqa: F401
+from . import heads16  # noqa: F401
 
-__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads"]
+__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads", "heads16"]

@@ -4,6 +4,8 @@
 // wide_products.h (wide_schedule.h) and, with HSMH_BACKWARD, the transposed pattern (hsw_common.h's stable counting sort, without its
 // CSR-index map) with the columns sorted the same way and max_heads doubles per row, the D words the row kernel writes and the column
 // kernel reads.  The kernels are in heads_attention.hip.  Nothing here touches a context or another pattern object.
+// The four hsmh16_* calls of include/hisparse_heads_bf16.h work on the same object with bf16 operands (heads16_attention.hip): the same
+// pattern, transposed pattern, D words and stream, nothing held twice.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -11,7 +13,9 @@
 #include <vector>
 
 #include "device_buffer.h"
+#include "heads16_attention.h"
 #include "heads_attention.h"
+#include "hisparse_heads_bf16.h"
 #include "hsmh_common.h"
 #include "wide_schedule.h"
 
@@ -101,6 +105,13 @@ int build(hsmh_pattern* p, const uint32_t* indptr, const uint32_t* indices) {
 int features_in(hsmh_pattern* p, DeviceBuffer<float>& dev, const float* host, uint32_t n, uint32_t w) {
     HSMH_HIP(p, dev.alloc_count(size_t(n) * w, 16));
     HSMH_HIP(p, hipMemcpyAsync(dev.get(), host, size_t(n) * w * 4, hipMemcpyHostToDevice, p->stream));
+    return HS_OK;
+}
+
+// The same for bf16 elements, ld = w (a multiple of 8)
+int features16_in(hsmh_pattern* p, DeviceBuffer<uint16_t>& dev, const uint16_t* host, uint32_t n, uint32_t w) {
+    HSMH_HIP(p, dev.alloc_count(size_t(n) * w, 16));
+    HSMH_HIP(p, hipMemcpyAsync(dev.get(), host, size_t(n) * w * 2, hipMemcpyHostToDevice, p->stream));
     return HS_OK;
 }
 
@@ -246,6 +257,89 @@ int hsmh_backward(hsmh_pattern* p, const float* q, const float* k, const float* 
         hipError_t e = hipMemcpyAsync(gq, d_gq.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(gk, d_gk.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(gv, d_gv.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+// ---- include/hisparse_heads_bf16.h: the same object, bf16 operands ----------------------------------------------------------------------
+int hsmh16_forward_device(hsmh_pattern* p, const uint16_t* q_dev, uint64_t ldq, const uint16_t* k_dev, uint64_t ldk, const uint16_t* v_dev, uint64_t ldv, uint32_t heads, uint32_t d,
+                          float scale, uint16_t* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward16(p->num_rows, p->num_cols, p->max_heads, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_heads16_forward(p->rows, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl, p->stream));
+    return HS_OK;
+}
+
+int hsmh16_forward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint32_t heads, uint32_t d, float scale, uint16_t* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward16_host(p->num_rows, p->num_cols, p->max_heads, q, k, v, heads, d, scale, y, lse, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<uint16_t> d_q, d_k, d_v, d_y;      // transient (the host form is synchronous and may allocate)
+    DeviceBuffer<float> d_lse;
+    if (int rc = features16_in(p, d_q, q, p->num_rows, w)) return rc;
+    if (int rc = features16_in(p, d_k, k, p->num_cols, w)) return rc;
+    if (int rc = features16_in(p, d_v, v, p->num_cols, w)) return rc;
+    HSMH_HIP(p, d_y.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_lse.alloc_count(size_t(p->num_rows) * heads, 16));
+    int rc = hsmh16_forward_device(p, d_q.get(), w, d_k.get(), w, d_v.get(), w, heads, d, scale, d_y.get(), w, lse ? d_lse.get() : nullptr, heads);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(y, d_y.get(), size_t(p->num_rows) * w * 2, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess && lse) e = hipMemcpyAsync(lse, d_lse.get(), size_t(p->num_rows) * heads * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+int hsmh16_backward_device(hsmh_pattern* p, const uint16_t* q_dev, uint64_t ldq, const uint16_t* k_dev, uint64_t ldk, const uint16_t* v_dev, uint64_t ldv, const uint16_t* gy_dev,
+                           uint64_t ldgy, const float* lse_dev, uint64_t ldl, uint32_t heads, uint32_t d, float scale, uint16_t* gq_dev, uint64_t ldgq, uint16_t* gk_dev, uint64_t ldgk,
+                           uint16_t* gv_dev, uint64_t ldgv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward16(p->num_rows, p->num_cols, p->max_heads, p->backward, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale,
+                                                  gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_heads16_backward_rows(p->rows, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale, gq_dev, ldgq, p->dsum.get(), p->max_heads,
+                                             p->stream));
+    HSMH_HIP(p, launch_heads16_backward_cols(p->cols, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, p->dsum.get(), p->max_heads, heads, d, scale, gk_dev, ldgk,
+                                             gv_dev, ldgv, p->stream));
+    return HS_OK;
+}
+
+int hsmh16_backward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* gy, const float* lse, uint32_t heads, uint32_t d, float scale,
+                    uint16_t* gq, uint16_t* gk, uint16_t* gv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward16_host(p->num_rows, p->num_cols, p->max_heads, p->backward, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<uint16_t> d_q, d_k, d_v, d_gy, d_gq, d_gk, d_gv;      // transient (the host form is synchronous and may allocate)
+    DeviceBuffer<float> d_lse;
+    if (int rc = features16_in(p, d_q, q, p->num_rows, w)) return rc;
+    if (int rc = features16_in(p, d_k, k, p->num_cols, w)) return rc;
+    if (int rc = features16_in(p, d_v, v, p->num_cols, w)) return rc;
+    if (int rc = features16_in(p, d_gy, gy, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_lse, lse, p->num_rows, heads)) return rc;
+    HSMH_HIP(p, d_gq.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_gk.alloc_count(size_t(p->num_cols) * w, 16));
+    HSMH_HIP(p, d_gv.alloc_count(size_t(p->num_cols) * w, 16));
+    int rc = hsmh16_backward_device(p, d_q.get(), w, d_k.get(), w, d_v.get(), w, d_gy.get(), w, d_lse.get(), heads, heads, d, scale, d_gq.get(), w, d_gk.get(), w, d_gv.get(), w);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(gq, d_gq.get(), size_t(p->num_rows) * w * 2, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gk, d_gk.get(), size_t(p->num_cols) * w * 2, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gv, d_gv.get(), size_t(p->num_cols) * w * 2, hipMemcpyDeviceToHost, p->stream);
         if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
     }
     const hipError_t e = hipStreamSynchronize(p->stream);

@@ -134,6 +134,115 @@ inline int check_backward_host(uint32_t num_rows, uint32_t num_cols, uint32_t ma
     return hsab::check_overlaps(in, out, why);
 }
 
+// ---- the bf16 calls of include/hisparse_heads_bf16.h: the same rules over 2-byte elements, every reach in bytes ----------------------
+
+constexpr uint32_t kMaxWidth16 = 512;      // heads * d in elements: 1 KiB, the 64 chunks of the widest group as kMaxWidth words are
+
+// the SHAPES ACCEPTED paragraph of hisparse_heads_bf16.h
+inline int check_shape16(uint32_t heads, uint32_t d, uint32_t max_heads, std::string& why) {
+    const char* other = "; the fp32 calls hsmh_forward_device / hsmh_backward_device take operands widened to fp32, at d = 4 too";
+    if (d < 8 || d > 256 || (d & (d - 1))) {
+        why = std::string("d must be one of 8, 16, 32, 64, 128, 256 with bf16 operands (a head is whole 16-byte chunks of 8 elements)") + other;
+        return HS_ERR_BAD_ARG;
+    }
+    if (heads < 1 || heads > max_heads) {
+        why = std::string("heads must be 1 ... max_heads, the count given to hsmh_create") + other;
+        return HS_ERR_BAD_ARG;
+    }
+    if (uint64_t(heads) * d > kMaxWidth16) {
+        why = std::string("heads * d must be at most 512 with bf16 operands (a row of at most 1 KiB)") + other;
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+// one bf16 feature operand of w = heads * d elements per row
+inline int check_features16(const char* name, const void* p, uint64_t ld, uint32_t w, std::string& why) {
+    if (!p) {
+        why = std::string("null ") + name;
+        return HS_ERR_BAD_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(p) % 16) {
+        why = std::string(name) + " must be 16-byte aligned";
+        return HS_ERR_BAD_ARG;
+    }
+    if (ld % 8 || ld < w) {
+        why = std::string("the leading dimension of ") + name + " must be a multiple of 8 elements and at least heads * d";
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+// the bytes of a bf16 operand of n rows: to the end of the 16-byte chunk that holds element w - 1 of row n - 1 (w is a multiple of 8)
+inline uint64_t reach16(uint64_t n, uint64_t ld, uint32_t w) { return n ? ((n - 1) * ld + w) * 2 : 0; }
+
+// hsmh16_forward_device's arguments
+inline int check_forward16(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, const uint16_t* q, uint64_t ldq, const uint16_t* k, uint64_t ldk, const uint16_t* v, uint64_t ldv,
+                           uint32_t heads, uint32_t d, float scale, const uint16_t* y, uint64_t ldy, const float* lse, uint64_t ldl, std::string& why) {
+    if (int rc = check_shape16(heads, d, max_heads, why)) return rc;
+    const uint32_t w = heads * d;
+    if (int rc = check_features16("q", q, ldq, w, why)) return rc;
+    if (int rc = check_features16("k", k, ldk, w, why)) return rc;
+    if (int rc = check_features16("v", v, ldv, w, why)) return rc;
+    if (int rc = check_features16("y", y, ldy, w, why)) return rc;
+    if (lse)
+        if (int rc = check_lse(lse, ldl, heads, why)) return rc;
+    if (int rc = hsat::check_scale(scale, why)) return rc;
+    return hsat::check_overlaps(q, reach16(num_rows, ldq, w), k, reach16(num_cols, ldk, w), v, reach16(num_cols, ldv, w), y, reach16(num_rows, ldy, w), lse,
+                                lse_reach(num_rows, ldl, heads), why);
+}
+
+// hsmh16_forward's: ld = heads * d, ldl = heads, no alignment rule
+inline int check_forward16_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint32_t heads, uint32_t d,
+                                float scale, const uint16_t* y, const float* lse, std::string& why) {
+    if (int rc = check_shape16(heads, d, max_heads, why)) return rc;
+    if (!q || !k || !v || !y) {
+        why = "null argument";
+        return HS_ERR_BAD_ARG;
+    }
+    if (int rc = hsat::check_scale(scale, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 2, cb = uint64_t(num_cols) * heads * d * 2;
+    return hsat::check_overlaps(q, rb, k, cb, v, cb, y, rb, lse, uint64_t(num_rows) * heads * 4, why);
+}
+
+// hsmh16_backward_device's arguments
+inline int check_backward16(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool backward, const uint16_t* q, uint64_t ldq, const uint16_t* k, uint64_t ldk,
+                            const uint16_t* v, uint64_t ldv, const uint16_t* gy, uint64_t ldgy, const float* lse, uint64_t ldl, uint32_t heads, uint32_t d, float scale,
+                            const uint16_t* gq, uint64_t ldgq, const uint16_t* gk, uint64_t ldgk, const uint16_t* gv, uint64_t ldgv, std::string& why) {
+    if (int rc = check_backward_flag(backward, why)) return rc;
+    if (int rc = check_shape16(heads, d, max_heads, why)) return rc;
+    const uint32_t w = heads * d;
+    if (int rc = check_features16("q", q, ldq, w, why)) return rc;
+    if (int rc = check_features16("k", k, ldk, w, why)) return rc;
+    if (int rc = check_features16("v", v, ldv, w, why)) return rc;
+    if (int rc = check_features16("gy", gy, ldgy, w, why)) return rc;
+    if (int rc = check_lse(lse, ldl, heads, why)) return rc;
+    if (int rc = check_features16("gq", gq, ldgq, w, why)) return rc;
+    if (int rc = check_features16("gk", gk, ldgk, w, why)) return rc;
+    if (int rc = check_features16("gv", gv, ldgv, w, why)) return rc;
+    if (int rc = hsat::check_scale(scale, why)) return rc;
+    const hsab::Range in[5] = {{"q", q, reach16(num_rows, ldq, w)}, {"k", k, reach16(num_cols, ldk, w)}, {"v", v, reach16(num_cols, ldv, w)},
+                               {"gy", gy, reach16(num_rows, ldgy, w)}, {"lse", lse, lse_reach(num_rows, ldl, heads)}};
+    const hsab::Range out[3] = {{"gq", gq, reach16(num_rows, ldgq, w)}, {"gk", gk, reach16(num_cols, ldgk, w)}, {"gv", gv, reach16(num_cols, ldgv, w)}};
+    return hsab::check_overlaps(in, out, why);
+}
+
+// hsmh16_backward's: ld = heads * d, ldl = heads, no alignment rule
+inline int check_backward16_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool backward, const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* gy,
+                                 const float* lse, uint32_t heads, uint32_t d, float scale, const uint16_t* gq, const uint16_t* gk, const uint16_t* gv, std::string& why) {
+    if (int rc = check_backward_flag(backward, why)) return rc;
+    if (int rc = check_shape16(heads, d, max_heads, why)) return rc;
+    if (!q || !k || !v || !gy || !lse || !gq || !gk || !gv) {
+        why = "null argument";
+        return HS_ERR_BAD_ARG;
+    }
+    if (int rc = hsat::check_scale(scale, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 2, cb = uint64_t(num_cols) * heads * d * 2;
+    const hsab::Range in[5] = {{"q", q, rb}, {"k", k, cb}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, uint64_t(num_rows) * heads * 4}};
+    const hsab::Range out[3] = {{"gq", gq, rb}, {"gk", gk, cb}, {"gv", gv, cb}};
+    return hsab::check_overlaps(in, out, why);
+}
+
 }  // namespace hsmh
 }  // namespace hisparse
 

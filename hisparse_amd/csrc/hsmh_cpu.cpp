@@ -9,13 +9,17 @@
 // Arithmetic = the kernels' (heads_attention.hip), the header's ARITHMETIC paragraph: one fp32 multiply per product (built with
 // -ffp-contract=off), added in double, s rounded once; t = scale * s in fp32; everything after that in double, one rounding per output
 // word.
+// The four hsmh16_* calls of include/hisparse_heads_bf16.h run the same loops over bf16 elements (widen / narrow below): the operands
+// widened exactly, the same sums, and each output word rounded to fp32 and then to bf16.
 // No dependency beyond the headers and hsmh_common.h: tests/cpp/test_heads_cpu.cpp compiles this file alone under the sanitizers.
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "hisparse_heads_bf16.h"
 #include "hsmh_common.h"
 
 struct hsmh_pattern {
@@ -35,27 +39,46 @@ int fail(hsmh_pattern* p, int code, const std::string& msg) {
     return code;
 }
 
+// An element as the arithmetic reads it and an output word as it is stored.  fp32: the word itself and one rounding.  bf16 (a bit pattern
+// in uint16_t): the upper half of the fp32 of the same value, so widening is exact; an output word is rounded to fp32 and then to bf16,
+// to nearest even, and a NaN stays a NaN (the integer rounding alone would carry some NaNs into infinity).  +-inf and -0 survive.
+inline float widen(float x) { return x; }
+inline float widen(uint16_t x) {
+    const uint32_t bits = uint32_t(x) << 16;
+    float f;
+    std::memcpy(&f, &bits, 4);
+    return f;
+}
+inline void narrow(double x, float& out) { out = float(x); }
+inline void narrow(double x, uint16_t& out) {
+    const float f = float(x);
+    uint32_t bits;
+    std::memcpy(&bits, &f, 4);
+    out = f != f ? uint16_t((bits >> 16) | 0x0040u) : uint16_t((bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16);
+}
+
 // one head: the pointers are the head's first word of row 0, lse (may be null) its word of row 0
-void forward_head(const hsmh_pattern* p, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, uint32_t d, float scale, float* y, uint64_t ldy,
+template <typename T>
+void forward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, uint32_t d, float scale, T* y, uint64_t ldy,
                   float* lse, uint64_t ldl) {
     const float ninf = -std::numeric_limits<float>::infinity();
     std::vector<float> t;
     std::vector<double> acc(d);
     for (uint32_t r = 0; r < p->num_rows; ++r) {
         const uint64_t lo = p->indptr[r], hi = p->indptr[r + 1];
-        float* dst = y + uint64_t(r) * ldy;
+        T* dst = y + uint64_t(r) * ldy;
         if (lo == hi) {
-            for (uint32_t j = 0; j < d; ++j) dst[j] = 0.0f;
+            for (uint32_t j = 0; j < d; ++j) dst[j] = T(0);
             if (lse) lse[uint64_t(r) * ldl] = ninf;
             continue;
         }
-        const float* a = q + uint64_t(r) * ldq;
+        const T* a = q + uint64_t(r) * ldq;
         t.resize(hi - lo);
         float m = ninf;      // one of the t words; a NaN is never the maximum
         for (uint64_t e = lo; e < hi; ++e) {
-            const float* b = k + uint64_t(p->indices[e]) * ldk;
+            const T* b = k + uint64_t(p->indices[e]) * ldk;
             double s = 0.0;
-            for (uint32_t j = 0; j < d; ++j) s += double(a[j] * b[j]);
+            for (uint32_t j = 0; j < d; ++j) s += double(widen(a[j]) * widen(b[j]));
             t[e - lo] = scale * float(s);
             m = std::fmax(m, t[e - lo]);
         }
@@ -64,28 +87,29 @@ void forward_head(const hsmh_pattern* p, const float* q, uint64_t ldq, const flo
         for (uint64_t e = lo; e < hi; ++e) {
             // a -inf score weighs exactly 0, also while the maximum is -inf itself; a NaN, or +inf under a maximum of +inf, gives NaN
             const double w = t[e - lo] == ninf ? 0.0 : std::exp(double(t[e - lo]) - double(m));
-            const float* b = v + uint64_t(p->indices[e]) * ldv;
+            const T* b = v + uint64_t(p->indices[e]) * ldv;
             l += w;
-            for (uint32_t j = 0; j < d; ++j) acc[j] += w * double(b[j]);
+            for (uint32_t j = 0; j < d; ++j) acc[j] += w * double(widen(b[j]));
         }
-        for (uint32_t j = 0; j < d; ++j) dst[j] = float(acc[j] / l);
+        for (uint32_t j = 0; j < d; ++j) narrow(acc[j] / l, dst[j]);
         if (lse) lse[uint64_t(r) * ldl] = float(double(m) + std::log(l));
     }
 }
 
-void backward_head(const hsmh_pattern* p, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, const float* gy, uint64_t ldgy, const float* lse,
-                   uint64_t ldl, uint32_t d, float scale, float* gq, uint64_t ldgq, float* gk, uint64_t ldgk, float* gv, uint64_t ldgv) {
+template <typename T>
+void backward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, const T* gy, uint64_t ldgy, const float* lse, uint64_t ldl,
+                   uint32_t d, float scale, T* gq, uint64_t ldgq, T* gk, uint64_t ldgk, T* gv, uint64_t ldgv) {
     std::vector<double> w, gp, row(d);
     std::vector<double> sum_k(size_t(p->num_cols) * d, 0.0), sum_v(size_t(p->num_cols) * d, 0.0);
     for (uint32_t r = 0; r < p->num_rows; ++r) {
         const uint64_t lo = p->indptr[r], hi = p->indptr[r + 1];
-        float* dst = gq + uint64_t(r) * ldgq;
+        T* dst = gq + uint64_t(r) * ldgq;
         if (lo == hi) {
-            for (uint32_t j = 0; j < d; ++j) dst[j] = 0.0f;
+            for (uint32_t j = 0; j < d; ++j) dst[j] = T(0);
             continue;
         }
-        const float* a = q + uint64_t(r) * ldq;
-        const float* g = gy + uint64_t(r) * ldgy;
+        const T* a = q + uint64_t(r) * ldq;
+        const T* g = gy + uint64_t(r) * ldgy;
         // a word that is not finite (a dead or bad row of the forward) makes every weight of the row's head NaN
         const float lw = lse[uint64_t(r) * ldl];
         const double l = std::isfinite(lw) ? double(lw) : std::numeric_limits<double>::quiet_NaN();
@@ -93,11 +117,11 @@ void backward_head(const hsmh_pattern* p, const float* q, uint64_t ldq, const fl
         gp.resize(hi - lo);
         double dsum = 0.0;
         for (uint64_t e = lo; e < hi; ++e) {
-            const float* b = k + uint64_t(p->indices[e]) * ldk;
-            const float* c = v + uint64_t(p->indices[e]) * ldv;
+            const T* b = k + uint64_t(p->indices[e]) * ldk;
+            const T* c = v + uint64_t(p->indices[e]) * ldv;
             double s = 0.0, x = 0.0;
-            for (uint32_t j = 0; j < d; ++j) s += double(a[j] * b[j]);
-            for (uint32_t j = 0; j < d; ++j) x += double(g[j] * c[j]);
+            for (uint32_t j = 0; j < d; ++j) s += double(widen(a[j]) * widen(b[j]));
+            for (uint32_t j = 0; j < d; ++j) x += double(widen(g[j]) * widen(c[j]));
             w[e - lo] = std::exp(double(scale * float(s)) - l);      // a -inf score under a finite lse weighs exactly 0
             gp[e - lo] = x;
             dsum += w[e - lo] * x;
@@ -106,35 +130,37 @@ void backward_head(const hsmh_pattern* p, const float* q, uint64_t ldq, const fl
         for (uint64_t e = lo; e < hi; ++e) {
             const uint32_t c = p->indices[e];
             const double pe = w[e - lo], gs = double(scale) * (pe * (gp[e - lo] - dsum));
-            const float* b = k + uint64_t(c) * ldk;
+            const T* b = k + uint64_t(c) * ldk;
             double* to_k = sum_k.data() + size_t(c) * d;
             double* to_v = sum_v.data() + size_t(c) * d;
             for (uint32_t j = 0; j < d; ++j) {
-                row[j] += gs * double(b[j]);
-                to_k[j] += gs * double(a[j]);
-                to_v[j] += pe * double(g[j]);
+                row[j] += gs * double(widen(b[j]));
+                to_k[j] += gs * double(widen(a[j]));
+                to_v[j] += pe * double(widen(g[j]));
             }
         }
-        for (uint32_t j = 0; j < d; ++j) dst[j] = float(row[j]);
+        for (uint32_t j = 0; j < d; ++j) narrow(row[j], dst[j]);
     }
     for (uint32_t c = 0; c < p->num_cols; ++c) {
         for (uint32_t j = 0; j < d; ++j) {
-            gk[uint64_t(c) * ldgk + j] = float(sum_k[size_t(c) * d + j]);
-            gv[uint64_t(c) * ldgv + j] = float(sum_v[size_t(c) * d + j]);
+            narrow(sum_k[size_t(c) * d + j], gk[uint64_t(c) * ldgk + j]);
+            narrow(sum_v[size_t(c) * d + j], gv[uint64_t(c) * ldgv + j]);
         }
     }
 }
 
-void forward(const hsmh_pattern* p, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, uint32_t heads, uint32_t d, float scale, float* y,
-             uint64_t ldy, float* lse, uint64_t ldl) {
+template <typename T>
+void forward(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, uint32_t heads, uint32_t d, float scale, T* y, uint64_t ldy,
+             float* lse, uint64_t ldl) {
     for (uint32_t h = 0; h < heads; ++h) {
         const uint32_t at = h * d;
         forward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, d, scale, y + at, ldy, lse ? lse + h : nullptr, ldl);
     }
 }
 
-void backward(const hsmh_pattern* p, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, const float* gy, uint64_t ldgy, const float* lse,
-              uint64_t ldl, uint32_t heads, uint32_t d, float scale, float* gq, uint64_t ldgq, float* gk, uint64_t ldgk, float* gv, uint64_t ldgv) {
+template <typename T>
+void backward(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, const T* gy, uint64_t ldgy, const float* lse, uint64_t ldl,
+              uint32_t heads, uint32_t d, float scale, T* gq, uint64_t ldgq, T* gk, uint64_t ldgk, T* gv, uint64_t ldgv) {
     for (uint32_t h = 0; h < heads; ++h) {
         const uint32_t at = h * d;
         backward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, gy + at, ldgy, lse + h, ldl, d, scale, gq + at, ldgq, gk + at, ldgk, gv + at, ldgv);
@@ -221,6 +247,48 @@ int hsmh_backward(hsmh_pattern* p, const float* q, const float* k, const float* 
     if (!p) return HS_ERR_BAD_ARG;
     std::string why;
     if (int rc = hisparse::hsmh::check_backward_host(p->num_rows, p->num_cols, p->max_heads, p->backward, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    backward(p, q, w, k, w, v, w, gy, w, lse, heads, heads, d, scale, gq, w, gk, w, gv, w);
+    return HS_OK;
+}
+
+// ---- include/hisparse_heads_bf16.h: the same object, bf16 operands ----------------------------------------------------------------------
+int hsmh16_forward_device(hsmh_pattern* p, const uint16_t* q_dev, uint64_t ldq, const uint16_t* k_dev, uint64_t ldk, const uint16_t* v_dev, uint64_t ldv, uint32_t heads, uint32_t d,
+                          float scale, uint16_t* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward16(p->num_rows, p->num_cols, p->max_heads, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    forward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl);
+    return HS_OK;
+}
+
+int hsmh16_forward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint32_t heads, uint32_t d, float scale, uint16_t* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward16_host(p->num_rows, p->num_cols, p->max_heads, q, k, v, heads, d, scale, y, lse, why)) return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    forward(p, q, w, k, w, v, w, heads, d, scale, y, w, lse, heads);
+    return HS_OK;
+}
+
+int hsmh16_backward_device(hsmh_pattern* p, const uint16_t* q_dev, uint64_t ldq, const uint16_t* k_dev, uint64_t ldk, const uint16_t* v_dev, uint64_t ldv, const uint16_t* gy_dev,
+                           uint64_t ldgy, const float* lse_dev, uint64_t ldl, uint32_t heads, uint32_t d, float scale, uint16_t* gq_dev, uint64_t ldgq, uint16_t* gk_dev, uint64_t ldgk,
+                           uint16_t* gv_dev, uint64_t ldgv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward16(p->num_rows, p->num_cols, p->max_heads, p->backward, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale,
+                                                  gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, why))
+        return fail(p, rc, why);
+    backward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv);
+    return HS_OK;
+}
+
+int hsmh16_backward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* gy, const float* lse, uint32_t heads, uint32_t d, float scale,
+                    uint16_t* gq, uint16_t* gk, uint16_t* gv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward16_host(p->num_rows, p->num_cols, p->max_heads, p->backward, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return fail(p, rc, why);
     const uint64_t w = uint64_t(heads) * d;
     backward(p, q, w, k, w, v, w, gy, w, lse, heads, heads, d, scale, gq, w, gk, w, gv, w);
     return HS_OK;
