@@ -9,6 +9,7 @@ Layout:
   attention_backward.py ctypes face of include/hisparse_attention_backward.h (the backward of that step, from lse to gQ, gK and gV)
   heads.py     ctypes face of include/hisparse_heads.h (multi-head attention over a CSR pattern, forward and backward, all heads per call)
   heads16.py   ctypes face of include/hisparse_heads_bf16.h (the same object with bf16 operands)
+  heads_bias.py ctypes face of include/hisparse_heads_bias.h (the same object with a per-entry, per-head additive bias and its gradient)
   datasets.py  the reference's benchmark matrices as seeded stand-ins
   sharding.py  row-block sharding of one matrix across the GPUs of a node (+ RCCL gather of y)
   csrc/        C++ / HIP sources of the two libraries and the `benchmark` driver
@@ -22,5 +23,6 @@ from . import attention  # noqa: F401
 from . import attention_backward  # noqa: F401
 from . import heads  # noqa: F401
 from . import heads16  # noqa: F401
+from . import heads_bias  # noqa: F401
 
-__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads", "heads16"]
+__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads", "heads16", "heads_bias"]

@@ -6,6 +6,9 @@
 // kernel reads.  The kernels are in heads_attention.hip.  Nothing here touches a context or another pattern object.
 // The four hsmh16_* calls of include/hisparse_heads_bf16.h work on the same object with bf16 operands (heads16_attention.hip): the same
 // pattern, transposed pattern, D words and stream, nothing held twice.
+// The five hsmhb_* calls of include/hisparse_heads_bias.h add a per-entry, per-head bias (heads_bias_attention.hip).  hsmhb_create is
+// hsmh_create that, with HSMH_BACKWARD, also keeps the shared sort's CSR-index map on the device (4 max(nnz, 1) bytes more): the column
+// side of the backward finds an entry's bias words and stores its gbias words through it.  hsmh_create builds the map and drops it.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -15,7 +18,9 @@
 #include "device_buffer.h"
 #include "heads16_attention.h"
 #include "heads_attention.h"
+#include "heads_bias_attention.h"
 #include "hisparse_heads_bf16.h"
+#include "hisparse_heads_bias.h"
 #include "hsmh_common.h"
 #include "wide_schedule.h"
 
@@ -25,12 +30,14 @@ struct hsmh_pattern {
     int device = 0;
     uint32_t num_rows = 0, num_cols = 0, max_heads = 0;
     bool backward = false;
+    bool map = false;      // hsmhb_create with HSMH_BACKWARD: perm is kept
     uint64_t nnz = 0;
     uint64_t device_bytes = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     DeviceBuffer<uint32_t> ptr, idx, list;         // the pattern and its rows by class
     DeviceBuffer<uint32_t> cptr, crow, clist;      // with HSMH_BACKWARD: the transposed pattern and its columns by class
+    DeviceBuffer<uint32_t> perm;                   // with the map: the CSR index of every entry of the transposed pattern
     DeviceBuffer<double> dsum;                     // with HSMH_BACKWARD: D per row and head, [row][max_heads]: one backward call in flight per object
     WideSide rows, cols;
     std::string error;
@@ -73,12 +80,10 @@ int build(hsmh_pattern* p, const uint32_t* indptr, const uint32_t* indices) {
     HSMH_HIP(p, hipMemcpyAsync(p->ptr.get(), indptr, ptr_bytes, hipMemcpyHostToDevice, p->own_stream));
     HSMH_HIP(p, hipMemcpyAsync(p->list.get(), list.data(), list_bytes, hipMemcpyHostToDevice, p->own_stream));
     if (p->nnz) HSMH_HIP(p, hipMemcpyAsync(p->idx.get(), indices, size_t(p->nnz) * 4, hipMemcpyHostToDevice, p->own_stream));
-    std::vector<uint32_t> cptr, crow, clist;      // alive until the synchronisation below
+    std::vector<uint32_t> cptr, crow, clist, perm;      // alive until the synchronisation below
     if (p->backward) {
-        {
-            std::vector<uint32_t> perm;      // the CSR index of every entry in column order: built by the shared sort, not kept
-            hisparse::hsw::build_transposed(p->num_rows, p->num_cols, indptr, indices, cptr, crow, perm);
-        }
+        hisparse::hsw::build_transposed(p->num_rows, p->num_cols, indptr, indices, cptr, crow, perm);      // perm: the CSR index of every entry in column order
+        if (!p->map) std::vector<uint32_t>().swap(perm);                                                      // built by the shared sort, kept for hsmhb_create only
         schedule(p->num_cols, cptr.data(), clist, p->cols.count);
         const size_t cptr_bytes = (size_t(p->num_cols) + 1) * 4, clist_bytes = size_t(p->num_cols) * 4, dsum_bytes = size_t(p->num_rows) * p->max_heads * 8;
         HSMH_HIP(p, p->cptr.alloc(cptr_bytes));
@@ -89,6 +94,11 @@ int build(hsmh_pattern* p, const uint32_t* indptr, const uint32_t* indices) {
         HSMH_HIP(p, hipMemcpyAsync(p->cptr.get(), cptr.data(), cptr_bytes, hipMemcpyHostToDevice, p->own_stream));
         HSMH_HIP(p, hipMemcpyAsync(p->clist.get(), clist.data(), clist_bytes, hipMemcpyHostToDevice, p->own_stream));
         if (p->nnz) HSMH_HIP(p, hipMemcpyAsync(p->crow.get(), crow.data(), size_t(p->nnz) * 4, hipMemcpyHostToDevice, p->own_stream));
+        if (p->map) {
+            HSMH_HIP(p, p->perm.alloc(entry_bytes));
+            p->device_bytes += entry_bytes;
+            if (p->nnz) HSMH_HIP(p, hipMemcpyAsync(p->perm.get(), perm.data(), size_t(p->nnz) * 4, hipMemcpyHostToDevice, p->own_stream));
+        }
     }
     HSMH_HIP(p, hipStreamSynchronize(p->own_stream));      // the host arrays (the caller's and the vectors here) are free again
     p->rows.ptr = p->ptr.get();
@@ -97,6 +107,7 @@ int build(hsmh_pattern* p, const uint32_t* indptr, const uint32_t* indices) {
     p->cols.ptr = p->cptr.get();
     p->cols.idx = p->crow.get();
     p->cols.list = p->clist.get();
+    p->cols.perm = p->map ? p->perm.get() : nullptr;      // read by the kernels of heads_bias_attention.hip only
     p->rows.entries = p->cols.entries = p->nnz;
     return HS_OK;
 }
@@ -115,11 +126,15 @@ int features16_in(hsmh_pattern* p, DeviceBuffer<uint16_t>& dev, const uint16_t* 
     return HS_OK;
 }
 
-}  // namespace
+// A per-entry host array of nnz x heads words on the device, ld = heads (a word at least, so that the pointer is never null)
+int entries_in(hsmh_pattern* p, DeviceBuffer<float>& dev, const float* host, uint32_t heads) {
+    HSMH_HIP(p, dev.alloc_count(std::max<size_t>(size_t(p->nnz) * heads, 1), 16));
+    if (p->nnz) HSMH_HIP(p, hipMemcpyAsync(dev.get(), host, size_t(p->nnz) * heads * 4, hipMemcpyHostToDevice, p->stream));
+    return HS_OK;
+}
 
-extern "C" {
-
-int hsmh_create(hsmh_pattern** out, int device_id, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, uint32_t max_heads, uint32_t flags) {
+// hsmh_create and hsmhb_create: keep_map asks for the entry map beside the transposed pattern
+int create(hsmh_pattern** out, int device_id, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, uint32_t max_heads, uint32_t flags, bool keep_map) {
     if (!out) return fail(nullptr, HS_ERR_BAD_ARG, "null pattern pointer");
     *out = nullptr;
     std::string why;
@@ -139,6 +154,7 @@ int hsmh_create(hsmh_pattern** out, int device_id, uint32_t num_rows, uint32_t n
     p->num_cols = num_cols;
     p->max_heads = max_heads;
     p->backward = (flags & HSMH_BACKWARD) != 0;
+    p->map = keep_map && p->backward;
     p->nnz = indptr[num_rows];
     p->rows.compute_units = p->cols.compute_units = uint32_t(prop.multiProcessorCount);
     if (int rc = build(p, indptr, indices)) {
@@ -149,6 +165,14 @@ int hsmh_create(hsmh_pattern** out, int device_id, uint32_t num_rows, uint32_t n
     }
     *out = p;
     return HS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hsmh_create(hsmh_pattern** out, int device_id, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, uint32_t max_heads, uint32_t flags) {
+    return create(out, device_id, num_rows, num_cols, indptr, indices, max_heads, flags, false);
 }
 
 int hsmh_destroy(hsmh_pattern* p) {
@@ -340,6 +364,98 @@ int hsmh16_backward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const
         hipError_t e = hipMemcpyAsync(gq, d_gq.get(), size_t(p->num_rows) * w * 2, hipMemcpyDeviceToHost, p->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(gk, d_gk.get(), size_t(p->num_cols) * w * 2, hipMemcpyDeviceToHost, p->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(gv, d_gv.get(), size_t(p->num_cols) * w * 2, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+// ---- include/hisparse_heads_bias.h: the same object, a bias per entry and head ----------------------------------------------------------
+int hsmhb_create(hsmh_pattern** out, int device_id, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, uint32_t max_heads, uint32_t flags) {
+    return create(out, device_id, num_rows, num_cols, indptr, indices, max_heads, flags, true);
+}
+
+int hsmhb_forward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* bias_dev, uint64_t ldb,
+                         uint32_t heads, uint32_t d, float scale, float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_bias(p->num_rows, p->num_cols, p->max_heads, p->nnz, q_dev, ldq, k_dev, ldk, v_dev, ldv, bias_dev, ldb, heads, d, scale, y_dev, ldy,
+                                                    lse_dev, ldl, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_biased_forward(p->rows, q_dev, ldq, k_dev, ldk, v_dev, ldv, bias_dev, ldb, heads, d, scale, y_dev, ldy, lse_dev, ldl, p->stream));
+    return HS_OK;
+}
+
+int hsmhb_forward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* bias, uint32_t heads, uint32_t d, float scale, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_bias_host(p->num_rows, p->num_cols, p->max_heads, p->nnz, q, k, v, bias, heads, d, scale, y, lse, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<float> d_q, d_k, d_v, d_b, d_y, d_lse;      // transient (the host form is synchronous and may allocate)
+    if (int rc = features_in(p, d_q, q, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_k, k, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_v, v, p->num_cols, w)) return rc;
+    if (int rc = entries_in(p, d_b, bias, heads)) return rc;
+    HSMH_HIP(p, d_y.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_lse.alloc_count(size_t(p->num_rows) * heads, 16));
+    int rc = hsmhb_forward_device(p, d_q.get(), w, d_k.get(), w, d_v.get(), w, d_b.get(), heads, heads, d, scale, d_y.get(), w, lse ? d_lse.get() : nullptr, heads);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(y, d_y.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess && lse) e = hipMemcpyAsync(lse, d_lse.get(), size_t(p->num_rows) * heads * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+int hsmhb_backward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* gy_dev, uint64_t ldgy,
+                          const float* lse_dev, uint64_t ldl, const float* bias_dev, uint64_t ldb, uint32_t heads, uint32_t d, float scale, float* gq_dev, uint64_t ldgq,
+                          float* gk_dev, uint64_t ldgk, float* gv_dev, uint64_t ldgv, float* gbias_dev, uint64_t ldgb) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_bias(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, bias_dev, ldb,
+                                                     heads, d, scale, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, gbias_dev, ldgb, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_biased_rows(p->rows, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, bias_dev, ldb, heads, d, scale, gq_dev, ldgq, p->dsum.get(), p->max_heads,
+                                   p->stream));
+    HSMH_HIP(p, launch_biased_cols(p->cols, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, p->dsum.get(), p->max_heads, bias_dev, ldb, heads, d, scale, gk_dev, ldgk,
+                                   gv_dev, ldgv, gbias_dev, ldgb, p->stream));
+    return HS_OK;
+}
+
+int hsmhb_backward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* gy, const float* lse, const float* bias, uint32_t heads, uint32_t d, float scale,
+                   float* gq, float* gk, float* gv, float* gbias) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_bias_host(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz, q, k, v, gy, lse, bias, heads, d, scale, gq, gk, gv, gbias, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<float> d_q, d_k, d_v, d_gy, d_lse, d_b, d_gq, d_gk, d_gv, d_gb;      // transient (the host form is synchronous and may allocate)
+    if (int rc = features_in(p, d_q, q, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_k, k, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_v, v, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_gy, gy, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_lse, lse, p->num_rows, heads)) return rc;
+    if (int rc = entries_in(p, d_b, bias, heads)) return rc;
+    HSMH_HIP(p, d_gq.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_gk.alloc_count(size_t(p->num_cols) * w, 16));
+    HSMH_HIP(p, d_gv.alloc_count(size_t(p->num_cols) * w, 16));
+    if (gbias) HSMH_HIP(p, d_gb.alloc_count(std::max<size_t>(size_t(p->nnz) * heads, 1), 16));
+    int rc = hsmhb_backward_device(p, d_q.get(), w, d_k.get(), w, d_v.get(), w, d_gy.get(), w, d_lse.get(), heads, d_b.get(), heads, heads, d, scale, d_gq.get(), w, d_gk.get(), w,
+                                   d_gv.get(), w, gbias ? d_gb.get() : nullptr, heads);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(gq, d_gq.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gk, d_gk.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gv, d_gv.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess && gbias && p->nnz) e = hipMemcpyAsync(gbias, d_gb.get(), size_t(p->nnz) * heads * 4, hipMemcpyDeviceToHost, p->stream);
         if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
     }
     const hipError_t e = hipStreamSynchronize(p->stream);

@@ -1,7 +1,8 @@
 // hsmh_common.h — what the two implementations of include/hisparse_heads.h share (hsmh_api.cpp on the HIP runtime, hsmh_cpu.cpp on the
 // host): the argument checks, so that both refuse the same calls with the same codes.  Built from hsat_common.h's checks (the pattern,
 // scale, the reach of an operand), hsab_common.h's overlap check of the backward and hsw_common.h's checks of one operand, all taken at
-// the width heads * d.  Host code only.
+// the width heads * d.  The calls with a bias of include/hisparse_heads_bias.h add the checks of their two per-entry arrays at the end.
+// Host code only.
 #ifndef HISPARSE_HSMH_COMMON_H_
 #define HISPARSE_HSMH_COMMON_H_
 
@@ -241,6 +242,105 @@ inline int check_backward16_host(uint32_t num_rows, uint32_t num_cols, uint32_t 
     const hsab::Range in[5] = {{"q", q, rb}, {"k", k, cb}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, uint64_t(num_rows) * heads * 4}};
     const hsab::Range out[3] = {{"gq", gq, rb}, {"gk", gk, cb}, {"gv", gv, cb}};
     return hsab::check_overlaps(in, out, why);
+}
+
+// ---- the calls with a bias of include/hisparse_heads_bias.h: the fp32 rules, and those of the two per-entry arrays --------------------
+
+// bias or gbias: nnz entries of ld words, `heads` of them used
+inline int check_bias(const char* name, const float* b, uint64_t ld, uint32_t heads, std::string& why) {
+    if (int rc = hsw::check_entries(name, b, why)) return rc;
+    if (ld < heads) {
+        why = std::string("the leading dimension of ") + name + " must be at least heads";
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+inline uint64_t bias_reach(uint64_t nnz, uint64_t ld, uint32_t heads) { return nnz ? ((nnz - 1) * ld + heads) * 4 : 0; }
+
+// an output of a call against one more input
+inline int check_apart(const char* out_name, const void* out, uint64_t out_bytes, const char* in_name, const void* in, uint64_t in_bytes, std::string& why) {
+    if (out && in && hsw::overlap(out, out_bytes, in, in_bytes)) {
+        why = std::string(out_name) + " overlaps " + in_name;
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+inline int check_map(bool map, std::string& why) {
+    if (!map) {
+        why = "the object holds no entry map: the backward with a bias needs an object from hsmhb_create with HSMH_BACKWARD";
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+// hsmhb_forward_device's arguments: hsmh_forward_device's, and bias as one more input
+inline int check_forward_bias(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, uint64_t nnz, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v,
+                              uint64_t ldv, const float* bias, uint64_t ldb, uint32_t heads, uint32_t d, float scale, const float* y, uint64_t ldy, const float* lse, uint64_t ldl,
+                              std::string& why) {
+    if (int rc = check_forward(num_rows, num_cols, max_heads, q, ldq, k, ldk, v, ldv, heads, d, scale, y, ldy, lse, ldl, why)) return rc;
+    if (int rc = check_bias("bias", bias, ldb, heads, why)) return rc;
+    const uint64_t bb = bias_reach(nnz, ldb, heads);
+    if (int rc = check_apart("y", y, hsat::reach(num_rows, ldy, heads * d), "bias", bias, bb, why)) return rc;
+    return check_apart("lse", lse, lse_reach(num_rows, ldl, heads), "bias", bias, bb, why);
+}
+
+// hsmhb_forward's: ld = heads * d, ldl = ldb = heads, no alignment rule
+inline int check_forward_bias_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, uint64_t nnz, const float* q, const float* k, const float* v, const float* bias,
+                                   uint32_t heads, uint32_t d, float scale, const float* y, const float* lse, std::string& why) {
+    if (int rc = check_forward_host(num_rows, num_cols, max_heads, q, k, v, heads, d, scale, y, lse, why)) return rc;
+    if (!bias) {
+        why = "null bias";
+        return HS_ERR_BAD_ARG;
+    }
+    const uint64_t bb = nnz * heads * 4;
+    if (int rc = check_apart("y", y, uint64_t(num_rows) * heads * d * 4, "bias", bias, bb, why)) return rc;
+    return check_apart("lse", lse, uint64_t(num_rows) * heads * 4, "bias", bias, bb, why);
+}
+
+// what the two backward forms share once the plain call's checks have passed: bias against gQ, gK and gV, gbias against everything
+inline int check_bias_overlaps(const hsab::Range (&in)[6], const hsab::Range (&out)[3], const float* gbias, uint64_t gbias_bytes, std::string& why) {
+    for (const hsab::Range& o : out)
+        if (int rc = check_apart(o.name, o.p, o.bytes, in[5].name, in[5].p, in[5].bytes, why)) return rc;
+    if (!gbias) return HS_OK;
+    for (const hsab::Range& i : in)
+        if (int rc = check_apart("gbias", gbias, gbias_bytes, i.name, i.p, i.bytes, why)) return rc;
+    for (const hsab::Range& o : out)
+        if (int rc = check_apart("gbias", gbias, gbias_bytes, o.name, o.p, o.bytes, why)) return rc;
+    return HS_OK;
+}
+
+// hsmhb_backward_device's arguments: the map, hsmh_backward_device's, bias as one more input and gbias (may be null) as one more output
+inline int check_backward_bias(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool map, uint64_t nnz, const float* q, uint64_t ldq, const float* k, uint64_t ldk,
+                               const float* v, uint64_t ldv, const float* gy, uint64_t ldgy, const float* lse, uint64_t ldl, const float* bias, uint64_t ldb, uint32_t heads, uint32_t d,
+                               float scale, const float* gq, uint64_t ldgq, const float* gk, uint64_t ldgk, const float* gv, uint64_t ldgv, const float* gbias, uint64_t ldgb,
+                               std::string& why) {
+    if (int rc = check_map(map, why)) return rc;
+    if (int rc = check_backward(num_rows, num_cols, max_heads, true, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, heads, d, scale, gq, ldgq, gk, ldgk, gv, ldgv, why)) return rc;
+    if (int rc = check_bias("bias", bias, ldb, heads, why)) return rc;
+    if (gbias)
+        if (int rc = check_bias("gbias", gbias, ldgb, heads, why)) return rc;
+    const uint32_t w = heads * d;
+    const hsab::Range in[6] = {{"q", q, hsat::reach(num_rows, ldq, w)}, {"k", k, hsat::reach(num_cols, ldk, w)}, {"v", v, hsat::reach(num_cols, ldv, w)},
+                               {"gy", gy, hsat::reach(num_rows, ldgy, w)}, {"lse", lse, lse_reach(num_rows, ldl, heads)}, {"bias", bias, bias_reach(nnz, ldb, heads)}};
+    const hsab::Range out[3] = {{"gq", gq, hsat::reach(num_rows, ldgq, w)}, {"gk", gk, hsat::reach(num_cols, ldgk, w)}, {"gv", gv, hsat::reach(num_cols, ldgv, w)}};
+    return check_bias_overlaps(in, out, gbias, bias_reach(nnz, ldgb, heads), why);
+}
+
+// hsmhb_backward's: ld = heads * d, ldl = ldb = ldgb = heads, no alignment rule
+inline int check_backward_bias_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool map, uint64_t nnz, const float* q, const float* k, const float* v, const float* gy,
+                                    const float* lse, const float* bias, uint32_t heads, uint32_t d, float scale, const float* gq, const float* gk, const float* gv,
+                                    const float* gbias, std::string& why) {
+    if (int rc = check_map(map, why)) return rc;
+    if (int rc = check_backward_host(num_rows, num_cols, max_heads, true, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return rc;
+    if (!bias) {
+        why = "null bias";
+        return HS_ERR_BAD_ARG;
+    }
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4, eb = nnz * heads * 4;
+    const hsab::Range in[6] = {{"q", q, rb}, {"k", k, cb}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, uint64_t(num_rows) * heads * 4}, {"bias", bias, eb}};
+    const hsab::Range out[3] = {{"gq", gq, rb}, {"gk", gk, cb}, {"gv", gv, cb}};
+    return check_bias_overlaps(in, out, gbias, eb, why);
 }
 
 }  // namespace hsmh

@@ -11,6 +11,8 @@
 // word.
 // The four hsmh16_* calls of include/hisparse_heads_bf16.h run the same loops over bf16 elements (widen / narrow below): the operands
 // widened exactly, the same sums, and each output word rounded to fp32 and then to bf16.
+// The five hsmhb_* calls of include/hisparse_heads_bias.h run the fp32 loops with one more fp32 add per score, t = (scale * s) + bias of
+// the entry and head, and store gB = P (GP - D) per entry and head, formed in double and rounded once, where gbias is given.
 // No dependency beyond the headers and hsmh_common.h: tests/cpp/test_heads_cpu.cpp compiles this file alone under the sanitizers.
 #include <cmath>
 #include <cstring>
@@ -20,11 +22,13 @@
 #include <vector>
 
 #include "hisparse_heads_bf16.h"
+#include "hisparse_heads_bias.h"
 #include "hsmh_common.h"
 
 struct hsmh_pattern {
     uint32_t num_rows = 0, num_cols = 0, max_heads = 0;
     bool backward = false;
+    bool map = false;      // hsmhb_create with HSMH_BACKWARD: what the device library keeps the entry map for
     std::vector<uint32_t> indptr, indices;
     std::string error;
     uint64_t nnz() const { return indptr.back(); }
@@ -60,7 +64,7 @@ inline void narrow(double x, uint16_t& out) {
 // one head: the pointers are the head's first word of row 0, lse (may be null) its word of row 0
 template <typename T>
 void forward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, uint32_t d, float scale, T* y, uint64_t ldy,
-                  float* lse, uint64_t ldl) {
+                  float* lse, uint64_t ldl, const float* bias = nullptr, uint64_t ldb = 0) {
     const float ninf = -std::numeric_limits<float>::infinity();
     std::vector<float> t;
     std::vector<double> acc(d);
@@ -80,6 +84,7 @@ void forward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, u
             double s = 0.0;
             for (uint32_t j = 0; j < d; ++j) s += double(widen(a[j]) * widen(b[j]));
             t[e - lo] = scale * float(s);
+            if (bias) t[e - lo] = t[e - lo] + bias[e * ldb];      // the second rounding of t (hisparse_heads_bias.h)
             m = std::fmax(m, t[e - lo]);
         }
         double l = 0.0;
@@ -98,7 +103,8 @@ void forward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, u
 
 template <typename T>
 void backward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, const T* gy, uint64_t ldgy, const float* lse, uint64_t ldl,
-                   uint32_t d, float scale, T* gq, uint64_t ldgq, T* gk, uint64_t ldgk, T* gv, uint64_t ldgv) {
+                   uint32_t d, float scale, T* gq, uint64_t ldgq, T* gk, uint64_t ldgk, T* gv, uint64_t ldgv, const float* bias = nullptr, uint64_t ldb = 0,
+                   float* gbias = nullptr, uint64_t ldgb = 0) {
     std::vector<double> w, gp, row(d);
     std::vector<double> sum_k(size_t(p->num_cols) * d, 0.0), sum_v(size_t(p->num_cols) * d, 0.0);
     for (uint32_t r = 0; r < p->num_rows; ++r) {
@@ -122,14 +128,17 @@ void backward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, 
             double s = 0.0, x = 0.0;
             for (uint32_t j = 0; j < d; ++j) s += double(widen(a[j]) * widen(b[j]));
             for (uint32_t j = 0; j < d; ++j) x += double(widen(g[j]) * widen(c[j]));
-            w[e - lo] = std::exp(double(scale * float(s)) - l);      // a -inf score under a finite lse weighs exactly 0
+            float t = scale * float(s);
+            if (bias) t = t + bias[e * ldb];
+            w[e - lo] = std::exp(double(t) - l);      // a -inf score under a finite lse weighs exactly 0
             gp[e - lo] = x;
             dsum += w[e - lo] * x;
         }
         row.assign(d, 0.0);
         for (uint64_t e = lo; e < hi; ++e) {
             const uint32_t c = p->indices[e];
-            const double pe = w[e - lo], gs = double(scale) * (pe * (gp[e - lo] - dsum));
+            const double pe = w[e - lo], gb = pe * (gp[e - lo] - dsum), gs = double(scale) * gb;
+            if (gbias) gbias[e * ldgb] = float(gb);
             const T* b = k + uint64_t(c) * ldk;
             double* to_k = sum_k.data() + size_t(c) * d;
             double* to_v = sum_v.data() + size_t(c) * d;
@@ -151,19 +160,21 @@ void backward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, 
 
 template <typename T>
 void forward(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, uint32_t heads, uint32_t d, float scale, T* y, uint64_t ldy,
-             float* lse, uint64_t ldl) {
+             float* lse, uint64_t ldl, const float* bias = nullptr, uint64_t ldb = 0) {
     for (uint32_t h = 0; h < heads; ++h) {
         const uint32_t at = h * d;
-        forward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, d, scale, y + at, ldy, lse ? lse + h : nullptr, ldl);
+        forward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, d, scale, y + at, ldy, lse ? lse + h : nullptr, ldl, bias ? bias + h : nullptr, ldb);
     }
 }
 
 template <typename T>
 void backward(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, const T* gy, uint64_t ldgy, const float* lse, uint64_t ldl,
-              uint32_t heads, uint32_t d, float scale, T* gq, uint64_t ldgq, T* gk, uint64_t ldgk, T* gv, uint64_t ldgv) {
+              uint32_t heads, uint32_t d, float scale, T* gq, uint64_t ldgq, T* gk, uint64_t ldgk, T* gv, uint64_t ldgv, const float* bias = nullptr, uint64_t ldb = 0,
+              float* gbias = nullptr, uint64_t ldgb = 0) {
     for (uint32_t h = 0; h < heads; ++h) {
         const uint32_t at = h * d;
-        backward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, gy + at, ldgy, lse + h, ldl, d, scale, gq + at, ldgq, gk + at, ldgk, gv + at, ldgv);
+        backward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, gy + at, ldgy, lse + h, ldl, d, scale, gq + at, ldgq, gk + at, ldgk, gv + at, ldgv, bias ? bias + h : nullptr, ldb,
+                      gbias ? gbias + h : nullptr, ldgb);
     }
 }
 
@@ -291,6 +302,56 @@ int hsmh16_backward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const
     if (int rc = hisparse::hsmh::check_backward16_host(p->num_rows, p->num_cols, p->max_heads, p->backward, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return fail(p, rc, why);
     const uint64_t w = uint64_t(heads) * d;
     backward(p, q, w, k, w, v, w, gy, w, lse, heads, heads, d, scale, gq, w, gk, w, gv, w);
+    return HS_OK;
+}
+
+// ---- include/hisparse_heads_bias.h: the same object, a bias per entry and head --------------------------------------------------------
+int hsmhb_create(hsmh_pattern** out, int device_id, uint32_t num_rows, uint32_t num_cols, const uint32_t* indptr, const uint32_t* indices, uint32_t max_heads, uint32_t flags) {
+    const int rc = hsmh_create(out, device_id, num_rows, num_cols, indptr, indices, max_heads, flags);
+    if (rc == HS_OK) (*out)->map = (*out)->backward;
+    return rc;
+}
+
+int hsmhb_forward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* bias_dev, uint64_t ldb,
+                         uint32_t heads, uint32_t d, float scale, float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_bias(p->num_rows, p->num_cols, p->max_heads, p->nnz(), q_dev, ldq, k_dev, ldk, v_dev, ldv, bias_dev, ldb, heads, d, scale, y_dev, ldy,
+                                                    lse_dev, ldl, why))
+        return fail(p, rc, why);
+    forward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl, bias_dev, ldb);
+    return HS_OK;
+}
+
+int hsmhb_forward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* bias, uint32_t heads, uint32_t d, float scale, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_bias_host(p->num_rows, p->num_cols, p->max_heads, p->nnz(), q, k, v, bias, heads, d, scale, y, lse, why)) return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    forward(p, q, w, k, w, v, w, heads, d, scale, y, w, lse, heads, bias, heads);
+    return HS_OK;
+}
+
+int hsmhb_backward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* gy_dev, uint64_t ldgy,
+                          const float* lse_dev, uint64_t ldl, const float* bias_dev, uint64_t ldb, uint32_t heads, uint32_t d, float scale, float* gq_dev, uint64_t ldgq,
+                          float* gk_dev, uint64_t ldgk, float* gv_dev, uint64_t ldgv, float* gbias_dev, uint64_t ldgb) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_bias(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz(), q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, bias_dev,
+                                                     ldb, heads, d, scale, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, gbias_dev, ldgb, why))
+        return fail(p, rc, why);
+    backward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, bias_dev, ldb, gbias_dev, ldgb);
+    return HS_OK;
+}
+
+int hsmhb_backward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* gy, const float* lse, const float* bias, uint32_t heads, uint32_t d, float scale,
+                   float* gq, float* gk, float* gv, float* gbias) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_bias_host(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz(), q, k, v, gy, lse, bias, heads, d, scale, gq, gk, gv, gbias, why))
+        return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    backward(p, q, w, k, w, v, w, gy, w, lse, heads, heads, d, scale, gq, w, gk, w, gv, w, bias, heads, gbias, heads);
     return HS_OK;
 }
 

@@ -66,12 +66,16 @@ class MultiHeadAttention:
             raise DeviceError(-4, f"indices holds {indices.size} entries, indptr reaches {int(indptr.max())}")
         if not 0 <= int(max_heads) < 2 ** 32:
             raise DeviceError(-1, f"max_heads must be 1 ... {MAX_HEADS}, not {max_heads}")
-        rc = lib().hsmh_create(C.byref(self._h), device_id, rows, cols, indptr.ctypes.data, indices.ctypes.data if indices.size else None, int(max_heads),
-                               BACKWARD if backward else 0)
+        rc = self._create()(C.byref(self._h), device_id, rows, cols, indptr.ctypes.data, indices.ctypes.data if indices.size else None, int(max_heads),
+                            BACKWARD if backward else 0)
         if rc != 0:
             raise DeviceError(rc, lib().hsmh_last_error(None).decode())
         self.num_rows, self.num_cols, self.max_heads = int(rows), int(cols), int(max_heads)
         self.nnz = self.info()["nnz"]
+
+    def _create(self):
+        """the create call of the object (heads_bias.BiasedMultiHeadAttention asks for hsmhb_create, same arguments)"""
+        return lib().hsmh_create
 
     def _check(self, rc):
         if rc != 0:
