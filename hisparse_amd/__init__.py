@@ -10,6 +10,7 @@ Layout:
   heads.py     ctypes face of include/hisparse_heads.h (multi-head attention over a CSR pattern, forward and backward, all heads per call)
   heads16.py   ctypes face of include/hisparse_heads_bf16.h (the same object with bf16 operands)
   heads_bias.py ctypes face of include/hisparse_heads_bias.h (the same object with a per-entry, per-head additive bias and its gradient)
+  heads_dropout.py ctypes face of include/hisparse_heads_dropout.h (the same object with dropout on the attention weights, no mask stored)
   datasets.py  the reference's benchmark matrices as seeded stand-ins
   sharding.py  row-block sharding of one matrix across the GPUs of a node (+ RCCL gather of y)
   csrc/        C++ / HIP sources of the two libraries and the `benchmark` driver
@@ -24,5 +25,6 @@ from . import attention_backward  # noqa: F401
 from . import heads  # noqa: F401
 from . import heads16  # noqa: F401
 from . import heads_bias  # noqa: F401
+from . import heads_dropout  # noqa: F401
 
-__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads", "heads16", "heads_bias"]
+__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads", "heads16", "heads_bias", "heads_dropout"]

@@ -9,6 +9,8 @@
 // The five hsmhb_* calls of include/hisparse_heads_bias.h add a per-entry, per-head bias (heads_bias_attention.hip).  hsmhb_create is
 // hsmh_create that, with HSMH_BACKWARD, also keeps the shared sort's CSR-index map on the device (4 max(nnz, 1) bytes more): the column
 // side of the backward finds an entry's bias words and stores its gbias words through it.  hsmh_create builds the map and drops it.
+// The five hsmhd_* calls of include/hisparse_heads_dropout.h add dropout on the attention weights, with or without a bias
+// (heads_dropout_attention.hip): no new object and no memory; the backward keys its column side's draws through the same map.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -19,8 +21,10 @@
 #include "heads16_attention.h"
 #include "heads_attention.h"
 #include "heads_bias_attention.h"
+#include "heads_dropout_attention.h"
 #include "hisparse_heads_bf16.h"
 #include "hisparse_heads_bias.h"
+#include "hisparse_heads_dropout.h"
 #include "hsmh_common.h"
 #include "wide_schedule.h"
 
@@ -462,5 +466,103 @@ int hsmhb_backward(hsmh_pattern* p, const float* q, const float* k, const float*
     if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
     return rc;
 }
+
+// ---- include/hisparse_heads_dropout.h: the same object, dropout on the attention weights, a bias or none ----------------------------------
+int hsmhd_forward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* bias_dev, uint64_t ldb,
+                         uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed, uint64_t offset, float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_dropout(p->num_rows, p->num_cols, p->max_heads, p->nnz, q_dev, ldq, k_dev, ldk, v_dev, ldv, bias_dev, ldb, heads, d, scale, drop_p, y_dev,
+                                                       ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_dropout_forward(p->rows, q_dev, ldq, k_dev, ldk, v_dev, ldv, bias_dev, ldb, heads, d, scale, hisparse::philox::dropout_of(drop_p, seed, offset), y_dev, ldy,
+                                       lse_dev, ldl, p->stream));
+    return HS_OK;
+}
+
+int hsmhd_forward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* bias, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed,
+                  uint64_t offset, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_dropout_host(p->num_rows, p->num_cols, p->max_heads, p->nnz, q, k, v, bias, heads, d, scale, drop_p, y, lse, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<float> d_q, d_k, d_v, d_b, d_y, d_lse;      // transient (the host form is synchronous and may allocate)
+    if (int rc = features_in(p, d_q, q, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_k, k, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_v, v, p->num_cols, w)) return rc;
+    if (bias)
+        if (int rc = entries_in(p, d_b, bias, heads)) return rc;
+    HSMH_HIP(p, d_y.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_lse.alloc_count(size_t(p->num_rows) * heads, 16));
+    int rc = hsmhd_forward_device(p, d_q.get(), w, d_k.get(), w, d_v.get(), w, bias ? d_b.get() : nullptr, heads, heads, d, scale, drop_p, seed, offset, d_y.get(), w,
+                                  lse ? d_lse.get() : nullptr, heads);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(y, d_y.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess && lse) e = hipMemcpyAsync(lse, d_lse.get(), size_t(p->num_rows) * heads * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+int hsmhd_backward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* gy_dev, uint64_t ldgy,
+                          const float* lse_dev, uint64_t ldl, const float* bias_dev, uint64_t ldb, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed, uint64_t offset,
+                          float* gq_dev, uint64_t ldgq, float* gk_dev, uint64_t ldgk, float* gv_dev, uint64_t ldgv, float* gbias_dev, uint64_t ldgb) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_dropout(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, bias_dev,
+                                                        ldb, heads, d, scale, drop_p, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, gbias_dev, ldgb, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    HSMH_HIP(p, launch_dropout_rows(p->rows, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, bias_dev, ldb, heads, d, scale, dr, gq_dev, ldgq, p->dsum.get(), p->max_heads,
+                                    p->stream));
+    HSMH_HIP(p, launch_dropout_cols(p->cols, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, p->dsum.get(), p->max_heads, bias_dev, ldb, heads, d, scale, dr, gk_dev, ldgk,
+                                    gv_dev, ldgv, gbias_dev, ldgb, p->stream));
+    return HS_OK;
+}
+
+int hsmhd_backward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* gy, const float* lse, const float* bias, uint32_t heads, uint32_t d, float scale,
+                   float drop_p, uint64_t seed, uint64_t offset, float* gq, float* gk, float* gv, float* gbias) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_dropout_host(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz, q, k, v, gy, lse, bias, heads, d, scale, drop_p, gq, gk, gv, gbias,
+                                                             why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<float> d_q, d_k, d_v, d_gy, d_lse, d_b, d_gq, d_gk, d_gv, d_gb;      // transient (the host form is synchronous and may allocate)
+    if (int rc = features_in(p, d_q, q, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_k, k, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_v, v, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_gy, gy, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_lse, lse, p->num_rows, heads)) return rc;
+    if (bias)
+        if (int rc = entries_in(p, d_b, bias, heads)) return rc;
+    HSMH_HIP(p, d_gq.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_gk.alloc_count(size_t(p->num_cols) * w, 16));
+    HSMH_HIP(p, d_gv.alloc_count(size_t(p->num_cols) * w, 16));
+    if (gbias) HSMH_HIP(p, d_gb.alloc_count(std::max<size_t>(size_t(p->nnz) * heads, 1), 16));
+    int rc = hsmhd_backward_device(p, d_q.get(), w, d_k.get(), w, d_v.get(), w, d_gy.get(), w, d_lse.get(), heads, bias ? d_b.get() : nullptr, heads, heads, d, scale, drop_p, seed, offset,
+                                   d_gq.get(), w, d_gk.get(), w, d_gv.get(), w, gbias ? d_gb.get() : nullptr, heads);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(gq, d_gq.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gk, d_gk.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gv, d_gv.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess && gbias && p->nnz) e = hipMemcpyAsync(gbias, d_gb.get(), size_t(p->nnz) * heads * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+// host code: no object, no device
+int hsmhd_keep_mask(uint64_t nnz, uint32_t heads, float drop_p, uint64_t seed, uint64_t offset, uint8_t* keep) { return hisparse::hsmh::keep_mask(nnz, heads, drop_p, seed, offset, keep); }
 
 }  // extern "C"

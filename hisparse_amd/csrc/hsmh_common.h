@@ -1,16 +1,19 @@
 // hsmh_common.h — what the two implementations of include/hisparse_heads.h share (hsmh_api.cpp on the HIP runtime, hsmh_cpu.cpp on the
 // host): the argument checks, so that both refuse the same calls with the same codes.  Built from hsat_common.h's checks (the pattern,
 // scale, the reach of an operand), hsab_common.h's overlap check of the backward and hsw_common.h's checks of one operand, all taken at
-// the width heads * d.  The calls with a bias of include/hisparse_heads_bias.h add the checks of their two per-entry arrays at the end.
-// Host code only.
+// the width heads * d.  The calls with a bias of include/hisparse_heads_bias.h add the checks of their two per-entry arrays, and the
+// calls with dropout of include/hisparse_heads_dropout.h those of drop_p and of a bias that may be null, at the end, with hsmhd_keep_mask
+// itself, which both libraries export.  Host code only.
 #ifndef HISPARSE_HSMH_COMMON_H_
 #define HISPARSE_HSMH_COMMON_H_
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 
 #include "hisparse_heads.h"
 #include "hsab_common.h"
+#include "philox.h"
 
 namespace hisparse {
 namespace hsmh {
@@ -266,9 +269,9 @@ inline int check_apart(const char* out_name, const void* out, uint64_t out_bytes
     return HS_OK;
 }
 
-inline int check_map(bool map, std::string& why) {
+inline int check_map(bool map, std::string& why, const char* with = "a bias") {
     if (!map) {
-        why = "the object holds no entry map: the backward with a bias needs an object from hsmhb_create with HSMH_BACKWARD";
+        why = std::string("the object holds no entry map: the backward with ") + with + " needs an object from hsmhb_create with HSMH_BACKWARD";
         return HS_ERR_BAD_ARG;
     }
     return HS_OK;
@@ -341,6 +344,91 @@ inline int check_backward_bias_host(uint32_t num_rows, uint32_t num_cols, uint32
     const hsab::Range in[6] = {{"q", q, rb}, {"k", k, cb}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, uint64_t(num_rows) * heads * 4}, {"bias", bias, eb}};
     const hsab::Range out[3] = {{"gq", gq, rb}, {"gk", gk, cb}, {"gv", gv, cb}};
     return check_bias_overlaps(in, out, gbias, eb, why);
+}
+
+// ---- the calls with dropout of include/hisparse_heads_dropout.h: the rules above with a bias that may be null, and drop_p ------------
+
+inline int check_drop(float drop_p, std::string& why) {
+    if (!std::isfinite(drop_p) || drop_p < 0.0f || drop_p >= 1.0f) {
+        why = "drop_p must be finite and in [0, 1)";
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+// hsmhd_forward_device's arguments: hsmhb_forward_device's with a bias, hsmh_forward_device's without, and drop_p
+inline int check_forward_dropout(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, uint64_t nnz, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v,
+                                 uint64_t ldv, const float* bias, uint64_t ldb, uint32_t heads, uint32_t d, float scale, float drop_p, const float* y, uint64_t ldy, const float* lse,
+                                 uint64_t ldl, std::string& why) {
+    if (int rc = bias ? check_forward_bias(num_rows, num_cols, max_heads, nnz, q, ldq, k, ldk, v, ldv, bias, ldb, heads, d, scale, y, ldy, lse, ldl, why)
+                      : check_forward(num_rows, num_cols, max_heads, q, ldq, k, ldk, v, ldv, heads, d, scale, y, ldy, lse, ldl, why))
+        return rc;
+    return check_drop(drop_p, why);
+}
+
+// hsmhd_forward's: ld = heads * d, ldl = ldb = heads, no alignment rule
+inline int check_forward_dropout_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, uint64_t nnz, const float* q, const float* k, const float* v, const float* bias,
+                                      uint32_t heads, uint32_t d, float scale, float drop_p, const float* y, const float* lse, std::string& why) {
+    if (int rc = bias ? check_forward_bias_host(num_rows, num_cols, max_heads, nnz, q, k, v, bias, heads, d, scale, y, lse, why)
+                      : check_forward_host(num_rows, num_cols, max_heads, q, k, v, heads, d, scale, y, lse, why))
+        return rc;
+    return check_drop(drop_p, why);
+}
+
+// hsmhd_backward_device's arguments: the map (it keys the column side's draws, with or without a bias), hsmhb_backward_device's with a
+// bias; without one hsmh_backward_device's and gbias (may be null) as one more output
+inline int check_backward_dropout(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool map, uint64_t nnz, const float* q, uint64_t ldq, const float* k, uint64_t ldk,
+                                  const float* v, uint64_t ldv, const float* gy, uint64_t ldgy, const float* lse, uint64_t ldl, const float* bias, uint64_t ldb, uint32_t heads,
+                                  uint32_t d, float scale, float drop_p, const float* gq, uint64_t ldgq, const float* gk, uint64_t ldgk, const float* gv, uint64_t ldgv,
+                                  const float* gbias, uint64_t ldgb, std::string& why) {
+    if (int rc = check_map(map, why, "dropout")) return rc;
+    if (bias) {
+        if (int rc = check_backward_bias(num_rows, num_cols, max_heads, map, nnz, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, bias, ldb, heads, d, scale, gq, ldgq, gk, ldgk, gv, ldgv,
+                                         gbias, ldgb, why))
+            return rc;
+        return check_drop(drop_p, why);
+    }
+    if (int rc = check_backward(num_rows, num_cols, max_heads, true, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, heads, d, scale, gq, ldgq, gk, ldgk, gv, ldgv, why)) return rc;
+    if (gbias)
+        if (int rc = check_bias("gbias", gbias, ldgb, heads, why)) return rc;
+    const uint32_t w = heads * d;
+    const hsab::Range in[6] = {{"q", q, hsat::reach(num_rows, ldq, w)}, {"k", k, hsat::reach(num_cols, ldk, w)}, {"v", v, hsat::reach(num_cols, ldv, w)},
+                               {"gy", gy, hsat::reach(num_rows, ldgy, w)}, {"lse", lse, lse_reach(num_rows, ldl, heads)}, {"bias", nullptr, 0}};
+    const hsab::Range out[3] = {{"gq", gq, hsat::reach(num_rows, ldgq, w)}, {"gk", gk, hsat::reach(num_cols, ldgk, w)}, {"gv", gv, hsat::reach(num_cols, ldgv, w)}};
+    if (int rc = check_bias_overlaps(in, out, gbias, bias_reach(nnz, ldgb, heads), why)) return rc;
+    return check_drop(drop_p, why);
+}
+
+// hsmhd_backward's: ld = heads * d, ldl = ldb = ldgb = heads, no alignment rule
+inline int check_backward_dropout_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool map, uint64_t nnz, const float* q, const float* k, const float* v,
+                                       const float* gy, const float* lse, const float* bias, uint32_t heads, uint32_t d, float scale, float drop_p, const float* gq, const float* gk,
+                                       const float* gv, const float* gbias, std::string& why) {
+    if (int rc = check_map(map, why, "dropout")) return rc;
+    if (bias) {
+        if (int rc = check_backward_bias_host(num_rows, num_cols, max_heads, map, nnz, q, k, v, gy, lse, bias, heads, d, scale, gq, gk, gv, gbias, why)) return rc;
+        return check_drop(drop_p, why);
+    }
+    if (int rc = check_backward_host(num_rows, num_cols, max_heads, true, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4, eb = nnz * heads * 4;
+    const hsab::Range in[6] = {{"q", q, rb}, {"k", k, cb}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, uint64_t(num_rows) * heads * 4}, {"bias", nullptr, 0}};
+    const hsab::Range out[3] = {{"gq", gq, rb}, {"gk", gk, cb}, {"gv", gv, cb}};
+    if (int rc = check_bias_overlaps(in, out, gbias, eb, why)) return rc;
+    return check_drop(drop_p, why);
+}
+
+// hsmhd_keep_mask, whole: keep[e * heads + h] = 1 where (entry e, head h) is kept.  An entry's index is a 32-bit word of the counter.
+inline int keep_mask(uint64_t nnz, uint32_t heads, float drop_p, uint64_t seed, uint64_t offset, uint8_t* keep) {
+    std::string why;
+    if (check_drop(drop_p, why) || heads < 1 || heads > kMaxHeads || nnz > (uint64_t(1) << 32) || (nnz && !keep)) return HS_ERR_BAD_ARG;
+    const philox::Dropout dr = philox::dropout_of(drop_p, seed, offset);
+    for (uint64_t e = 0; e < nnz; ++e) {
+        for (uint32_t quad = 0; 4 * quad < heads; ++quad) {      // one draw serves four heads
+            const philox::Words x = philox::philox4x32_10(uint32_t(e), quad, dr.off0, dr.off1, dr.key0, dr.key1);
+            const uint32_t word[4] = {x.a, x.b, x.c, x.d};
+            for (uint32_t h = 4 * quad; h < heads && h < 4 * quad + 4; ++h) keep[e * heads + h] = word[h & 3u] >= dr.thr ? 1 : 0;
+        }
+    }
+    return HS_OK;
 }
 
 }  // namespace hsmh

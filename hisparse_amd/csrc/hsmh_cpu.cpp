@@ -13,6 +13,9 @@
 // widened exactly, the same sums, and each output word rounded to fp32 and then to bf16.
 // The five hsmhb_* calls of include/hisparse_heads_bias.h run the fp32 loops with one more fp32 add per score, t = (scale * s) + bias of
 // the entry and head, and store gB = P (GP - D) per entry and head, formed in double and rounded once, where gbias is given.
+// The five hsmhd_* calls of include/hisparse_heads_dropout.h run the fp32 loops with a weight w = keep(e, h) ? c : 0 per entry and head from
+// philox.h's generator: forward, l over all entries and the sums over w times the weight; backward, GP becomes w GP and gV takes w P.
+// With drop_p = 0 every w is 1.0 and the loops form the words of the calls without dropout.
 // No dependency beyond the headers and hsmh_common.h: tests/cpp/test_heads_cpu.cpp compiles this file alone under the sanitizers.
 #include <cmath>
 #include <cstring>
@@ -23,6 +26,7 @@
 
 #include "hisparse_heads_bf16.h"
 #include "hisparse_heads_bias.h"
+#include "hisparse_heads_dropout.h"
 #include "hsmh_common.h"
 
 struct hsmh_pattern {
@@ -64,7 +68,7 @@ inline void narrow(double x, uint16_t& out) {
 // one head: the pointers are the head's first word of row 0, lse (may be null) its word of row 0
 template <typename T>
 void forward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, uint32_t d, float scale, T* y, uint64_t ldy,
-                  float* lse, uint64_t ldl, const float* bias = nullptr, uint64_t ldb = 0) {
+                  float* lse, uint64_t ldl, const float* bias = nullptr, uint64_t ldb = 0, const hisparse::philox::Dropout* dr = nullptr, uint32_t head = 0) {
     const float ninf = -std::numeric_limits<float>::infinity();
     std::vector<float> t;
     std::vector<double> acc(d);
@@ -93,8 +97,9 @@ void forward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, u
             // a -inf score weighs exactly 0, also while the maximum is -inf itself; a NaN, or +inf under a maximum of +inf, gives NaN
             const double w = t[e - lo] == ninf ? 0.0 : std::exp(double(t[e - lo]) - double(m));
             const T* b = v + uint64_t(p->indices[e]) * ldv;
-            l += w;
-            for (uint32_t j = 0; j < d; ++j) acc[j] += w * double(widen(b[j]));
+            l += w;      // over every entry, dropped or not
+            const double wv = dr ? (hisparse::philox::keep(*dr, uint32_t(e), head) ? dr->c : 0.0) * w : w;
+            for (uint32_t j = 0; j < d; ++j) acc[j] += wv * double(widen(b[j]));
         }
         for (uint32_t j = 0; j < d; ++j) narrow(acc[j] / l, dst[j]);
         if (lse) lse[uint64_t(r) * ldl] = float(double(m) + std::log(l));
@@ -104,8 +109,8 @@ void forward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, u
 template <typename T>
 void backward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, const T* gy, uint64_t ldgy, const float* lse, uint64_t ldl,
                    uint32_t d, float scale, T* gq, uint64_t ldgq, T* gk, uint64_t ldgk, T* gv, uint64_t ldgv, const float* bias = nullptr, uint64_t ldb = 0,
-                   float* gbias = nullptr, uint64_t ldgb = 0) {
-    std::vector<double> w, gp, row(d);
+                   float* gbias = nullptr, uint64_t ldgb = 0, const hisparse::philox::Dropout* dr = nullptr, uint32_t head = 0) {
+    std::vector<double> w, gp, wt, row(d);
     std::vector<double> sum_k(size_t(p->num_cols) * d, 0.0), sum_v(size_t(p->num_cols) * d, 0.0);
     for (uint32_t r = 0; r < p->num_rows; ++r) {
         const uint64_t lo = p->indptr[r], hi = p->indptr[r + 1];
@@ -121,6 +126,7 @@ void backward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, 
         const double l = std::isfinite(lw) ? double(lw) : std::numeric_limits<double>::quiet_NaN();
         w.resize(hi - lo);
         gp.resize(hi - lo);
+        wt.assign(hi - lo, 1.0);
         double dsum = 0.0;
         for (uint64_t e = lo; e < hi; ++e) {
             const T* b = k + uint64_t(p->indices[e]) * ldk;
@@ -131,13 +137,17 @@ void backward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, 
             float t = scale * float(s);
             if (bias) t = t + bias[e * ldb];
             w[e - lo] = std::exp(double(t) - l);      // a -inf score under a finite lse weighs exactly 0
+            if (dr) {      // GP = w (gY . V): 1.0 x = x without dropout
+                wt[e - lo] = hisparse::philox::keep(*dr, uint32_t(e), head) ? dr->c : 0.0;
+                x = wt[e - lo] * x;
+            }
             gp[e - lo] = x;
             dsum += w[e - lo] * x;
         }
         row.assign(d, 0.0);
         for (uint64_t e = lo; e < hi; ++e) {
             const uint32_t c = p->indices[e];
-            const double pe = w[e - lo], gb = pe * (gp[e - lo] - dsum), gs = double(scale) * gb;
+            const double pe = w[e - lo], gb = pe * (gp[e - lo] - dsum), gs = double(scale) * gb, pw = dr ? wt[e - lo] * pe : pe;
             if (gbias) gbias[e * ldgb] = float(gb);
             const T* b = k + uint64_t(c) * ldk;
             double* to_k = sum_k.data() + size_t(c) * d;
@@ -145,7 +155,7 @@ void backward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, 
             for (uint32_t j = 0; j < d; ++j) {
                 row[j] += gs * double(widen(b[j]));
                 to_k[j] += gs * double(widen(a[j]));
-                to_v[j] += pe * double(widen(g[j]));
+                to_v[j] += pw * double(widen(g[j]));
             }
         }
         for (uint32_t j = 0; j < d; ++j) narrow(row[j], dst[j]);
@@ -160,21 +170,21 @@ void backward_head(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, 
 
 template <typename T>
 void forward(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, uint32_t heads, uint32_t d, float scale, T* y, uint64_t ldy,
-             float* lse, uint64_t ldl, const float* bias = nullptr, uint64_t ldb = 0) {
+             float* lse, uint64_t ldl, const float* bias = nullptr, uint64_t ldb = 0, const hisparse::philox::Dropout* dr = nullptr) {
     for (uint32_t h = 0; h < heads; ++h) {
         const uint32_t at = h * d;
-        forward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, d, scale, y + at, ldy, lse ? lse + h : nullptr, ldl, bias ? bias + h : nullptr, ldb);
+        forward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, d, scale, y + at, ldy, lse ? lse + h : nullptr, ldl, bias ? bias + h : nullptr, ldb, dr, h);
     }
 }
 
 template <typename T>
 void backward(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint64_t ldk, const T* v, uint64_t ldv, const T* gy, uint64_t ldgy, const float* lse, uint64_t ldl,
               uint32_t heads, uint32_t d, float scale, T* gq, uint64_t ldgq, T* gk, uint64_t ldgk, T* gv, uint64_t ldgv, const float* bias = nullptr, uint64_t ldb = 0,
-              float* gbias = nullptr, uint64_t ldgb = 0) {
+              float* gbias = nullptr, uint64_t ldgb = 0, const hisparse::philox::Dropout* dr = nullptr) {
     for (uint32_t h = 0; h < heads; ++h) {
         const uint32_t at = h * d;
         backward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, gy + at, ldgy, lse + h, ldl, d, scale, gq + at, ldgq, gk + at, ldgk, gv + at, ldgv, bias ? bias + h : nullptr, ldb,
-                      gbias ? gbias + h : nullptr, ldgb);
+                      gbias ? gbias + h : nullptr, ldgb, dr, h);
     }
 }
 
@@ -354,5 +364,57 @@ int hsmhb_backward(hsmh_pattern* p, const float* q, const float* k, const float*
     backward(p, q, w, k, w, v, w, gy, w, lse, heads, heads, d, scale, gq, w, gk, w, gv, w, bias, heads, gbias, heads);
     return HS_OK;
 }
+
+// ---- include/hisparse_heads_dropout.h: the same object, dropout on the attention weights, a bias or none --------------------------------
+int hsmhd_forward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* bias_dev, uint64_t ldb,
+                         uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed, uint64_t offset, float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_dropout(p->num_rows, p->num_cols, p->max_heads, p->nnz(), q_dev, ldq, k_dev, ldk, v_dev, ldv, bias_dev, ldb, heads, d, scale, drop_p, y_dev,
+                                                       ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    forward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl, bias_dev, ldb, &dr);
+    return HS_OK;
+}
+
+int hsmhd_forward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* bias, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed,
+                  uint64_t offset, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_dropout_host(p->num_rows, p->num_cols, p->max_heads, p->nnz(), q, k, v, bias, heads, d, scale, drop_p, y, lse, why)) return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    forward(p, q, w, k, w, v, w, heads, d, scale, y, w, lse, heads, bias, heads, &dr);
+    return HS_OK;
+}
+
+int hsmhd_backward_device(hsmh_pattern* p, const float* q_dev, uint64_t ldq, const float* k_dev, uint64_t ldk, const float* v_dev, uint64_t ldv, const float* gy_dev, uint64_t ldgy,
+                          const float* lse_dev, uint64_t ldl, const float* bias_dev, uint64_t ldb, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed, uint64_t offset,
+                          float* gq_dev, uint64_t ldgq, float* gk_dev, uint64_t ldgk, float* gv_dev, uint64_t ldgv, float* gbias_dev, uint64_t ldgb) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_dropout(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz(), q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, bias_dev,
+                                                        ldb, heads, d, scale, drop_p, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, gbias_dev, ldgb, why))
+        return fail(p, rc, why);
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    backward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, bias_dev, ldb, gbias_dev, ldgb, &dr);
+    return HS_OK;
+}
+
+int hsmhd_backward(hsmh_pattern* p, const float* q, const float* k, const float* v, const float* gy, const float* lse, const float* bias, uint32_t heads, uint32_t d, float scale,
+                   float drop_p, uint64_t seed, uint64_t offset, float* gq, float* gk, float* gv, float* gbias) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_dropout_host(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz(), q, k, v, gy, lse, bias, heads, d, scale, drop_p, gq, gk, gv, gbias,
+                                                             why))
+        return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    backward(p, q, w, k, w, v, w, gy, w, lse, heads, heads, d, scale, gq, w, gk, w, gv, w, bias, heads, gbias, heads, &dr);
+    return HS_OK;
+}
+
+int hsmhd_keep_mask(uint64_t nnz, uint32_t heads, float drop_p, uint64_t seed, uint64_t offset, uint8_t* keep) { return hisparse::hsmh::keep_mask(nnz, heads, drop_p, seed, offset, keep); }
 
 }  // extern "C"
