@@ -11,6 +11,8 @@
 // side of the backward finds an entry's bias words and stores its gbias words through it.  hsmh_create builds the map and drops it.
 // The five hsmhd_* calls of include/hisparse_heads_dropout.h add dropout on the attention weights, with or without a bias
 // (heads_dropout_attention.hip): no new object and no memory; the backward keys its column side's draws through the same map.
+// The four hsgat_* calls of include/hisparse_gat.h run the graph attention (GAT) step on the same object (gat_attention.hip): additive
+// scores from one word per node and head, the same pattern, transposed pattern, D words and stream, no map and no memory of their own.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -18,10 +20,12 @@
 #include <vector>
 
 #include "device_buffer.h"
+#include "gat_attention.h"
 #include "heads16_attention.h"
 #include "heads_attention.h"
 #include "heads_bias_attention.h"
 #include "heads_dropout_attention.h"
+#include "hisparse_gat.h"
 #include "hisparse_heads_bf16.h"
 #include "hisparse_heads_bias.h"
 #include "hisparse_heads_dropout.h"
@@ -564,5 +568,88 @@ int hsmhd_backward(hsmh_pattern* p, const float* q, const float* k, const float*
 
 // host code: no object, no device
 int hsmhd_keep_mask(uint64_t nnz, uint32_t heads, float drop_p, uint64_t seed, uint64_t offset, uint8_t* keep) { return hisparse::hsmh::keep_mask(nnz, heads, drop_p, seed, offset, keep); }
+
+// ---- include/hisparse_gat.h: the same object, additive (GAT) scores from one word per node and head ---------------------------------------
+int hsgat_forward_device(hsmh_pattern* p, const float* el_dev, uint64_t ldel, const float* er_dev, uint64_t lder, const float* v_dev, uint64_t ldv, uint32_t heads, uint32_t d,
+                         float slope, float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat_forward(p->num_rows, p->num_cols, p->max_heads, el_dev, ldel, er_dev, lder, v_dev, ldv, heads, d, slope, y_dev, ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_gat_forward(p->rows, el_dev, ldel, er_dev, lder, v_dev, ldv, heads, d, slope, y_dev, ldy, lse_dev, ldl, p->stream));
+    return HS_OK;
+}
+
+int hsgat_forward(hsmh_pattern* p, const float* el, const float* er, const float* v, uint32_t heads, uint32_t d, float slope, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat_forward_host(p->num_rows, p->num_cols, p->max_heads, el, er, v, heads, d, slope, y, lse, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<float> d_el, d_er, d_v, d_y, d_lse;      // transient (the host form is synchronous and may allocate)
+    if (int rc = features_in(p, d_el, el, p->num_rows, heads)) return rc;
+    if (int rc = features_in(p, d_er, er, p->num_cols, heads)) return rc;
+    if (int rc = features_in(p, d_v, v, p->num_cols, w)) return rc;
+    HSMH_HIP(p, d_y.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_lse.alloc_count(size_t(p->num_rows) * heads, 16));
+    int rc = hsgat_forward_device(p, d_el.get(), heads, d_er.get(), heads, d_v.get(), w, heads, d, slope, d_y.get(), w, lse ? d_lse.get() : nullptr, heads);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(y, d_y.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess && lse) e = hipMemcpyAsync(lse, d_lse.get(), size_t(p->num_rows) * heads * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+int hsgat_backward_device(hsmh_pattern* p, const float* el_dev, uint64_t ldel, const float* er_dev, uint64_t lder, const float* v_dev, uint64_t ldv, const float* gy_dev, uint64_t ldgy,
+                          const float* lse_dev, uint64_t ldl, uint32_t heads, uint32_t d, float slope, float* gel_dev, uint64_t ldgel, float* ger_dev, uint64_t ldger, float* gv_dev,
+                          uint64_t ldgv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat_backward(p->num_rows, p->num_cols, p->max_heads, p->backward, el_dev, ldel, er_dev, lder, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d,
+                                                    slope, gel_dev, ldgel, ger_dev, ldger, gv_dev, ldgv, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_gat_backward_rows(p->rows, el_dev, ldel, er_dev, lder, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, slope, gel_dev, ldgel, p->dsum.get(), p->max_heads,
+                                         p->stream));
+    HSMH_HIP(p, launch_gat_backward_cols(p->cols, el_dev, ldel, er_dev, lder, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, p->dsum.get(), p->max_heads, heads, d, slope, ger_dev, ldger,
+                                         gv_dev, ldgv, p->stream));
+    return HS_OK;
+}
+
+int hsgat_backward(hsmh_pattern* p, const float* el, const float* er, const float* v, const float* gy, const float* lse, uint32_t heads, uint32_t d, float slope, float* gel,
+                   float* ger, float* gv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat_backward_host(p->num_rows, p->num_cols, p->max_heads, p->backward, el, er, v, gy, lse, heads, d, slope, gel, ger, gv, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<float> d_el, d_er, d_v, d_gy, d_lse, d_gel, d_ger, d_gv;      // transient (the host form is synchronous and may allocate)
+    if (int rc = features_in(p, d_el, el, p->num_rows, heads)) return rc;
+    if (int rc = features_in(p, d_er, er, p->num_cols, heads)) return rc;
+    if (int rc = features_in(p, d_v, v, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_gy, gy, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_lse, lse, p->num_rows, heads)) return rc;
+    HSMH_HIP(p, d_gel.alloc_count(size_t(p->num_rows) * heads, 16));
+    HSMH_HIP(p, d_ger.alloc_count(size_t(p->num_cols) * heads, 16));
+    HSMH_HIP(p, d_gv.alloc_count(size_t(p->num_cols) * w, 16));
+    int rc = hsgat_backward_device(p, d_el.get(), heads, d_er.get(), heads, d_v.get(), w, d_gy.get(), w, d_lse.get(), heads, heads, d, slope, d_gel.get(), heads, d_ger.get(), heads,
+                                   d_gv.get(), w);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(gel, d_gel.get(), size_t(p->num_rows) * heads * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ger, d_ger.get(), size_t(p->num_cols) * heads * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gv, d_gv.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 // scale, the reach of an operand), hsab_common.h's overlap check of the backward and hsw_common.h's checks of one operand, all taken at
 // the width heads * d.  The calls with a bias of include/hisparse_heads_bias.h add the checks of their two per-entry arrays, and the
 // calls with dropout of include/hisparse_heads_dropout.h those of drop_p and of a bias that may be null, at the end, with hsmhd_keep_mask
-// itself, which both libraries export.  Host code only.
+// itself, which both libraries export; the calls of include/hisparse_gat.h (additive scores from one word per node and head) their
+// slope and the checks of the five head arrays, after that.  Host code only.
 #ifndef HISPARSE_HSMH_COMMON_H_
 #define HISPARSE_HSMH_COMMON_H_
 
@@ -429,6 +430,86 @@ inline int keep_mask(uint64_t nnz, uint32_t heads, float drop_p, uint64_t seed, 
         }
     }
     return HS_OK;
+}
+
+// ---- the calls of include/hisparse_gat.h: additive scores from one word per node and head, no Q, no K, no scale ----------------------
+
+inline int check_slope(float slope, std::string& why) {
+    if (!std::isfinite(slope) || slope < 0.0f) {      // -0.0f is not below zero: it counts as 0
+        why = "slope must be finite and at least 0";
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+// el, er, gel or ger: one row per node of ld words, `heads` of them used; the rules and the reach of lse
+inline int check_head_words(const char* name, const float* p, uint64_t ld, uint32_t heads, std::string& why) { return check_bias(name, p, ld, heads, why); }
+
+// hsgat_forward_device's arguments
+inline int check_gat_forward(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, const float* el, uint64_t ldel, const float* er, uint64_t lder, const float* v, uint64_t ldv,
+                             uint32_t heads, uint32_t d, float slope, const float* y, uint64_t ldy, const float* lse, uint64_t ldl, std::string& why) {
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    const uint32_t w = heads * d;
+    if (int rc = check_head_words("el", el, ldel, heads, why)) return rc;
+    if (int rc = check_head_words("er", er, lder, heads, why)) return rc;
+    if (int rc = hsw::check_features("v", v, ldv, w, why)) return rc;
+    if (int rc = hsw::check_features("y", y, ldy, w, why)) return rc;
+    if (lse)
+        if (int rc = check_lse(lse, ldl, heads, why)) return rc;
+    if (int rc = check_slope(slope, why)) return rc;
+    return hsat::check_overlaps(el, lse_reach(num_rows, ldel, heads), er, lse_reach(num_cols, lder, heads), v, hsat::reach(num_cols, ldv, w), y, hsat::reach(num_rows, ldy, w), lse,
+                                lse_reach(num_rows, ldl, heads), why);
+}
+
+// hsgat_forward's: ld = heads * d for V and Y, ld = heads for el, er and lse, no alignment rule
+inline int check_gat_forward_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, const float* el, const float* er, const float* v, uint32_t heads, uint32_t d, float slope,
+                                  const float* y, const float* lse, std::string& why) {
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    if (!el || !er || !v || !y) {
+        why = "null argument";
+        return HS_ERR_BAD_ARG;
+    }
+    if (int rc = check_slope(slope, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4;
+    return hsat::check_overlaps(el, uint64_t(num_rows) * heads * 4, er, uint64_t(num_cols) * heads * 4, v, cb, y, rb, lse, uint64_t(num_rows) * heads * 4, why);
+}
+
+// hsgat_backward_device's arguments
+inline int check_gat_backward(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool backward, const float* el, uint64_t ldel, const float* er, uint64_t lder, const float* v,
+                              uint64_t ldv, const float* gy, uint64_t ldgy, const float* lse, uint64_t ldl, uint32_t heads, uint32_t d, float slope, const float* gel, uint64_t ldgel,
+                              const float* ger, uint64_t ldger, const float* gv, uint64_t ldgv, std::string& why) {
+    if (int rc = check_backward_flag(backward, why)) return rc;
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    const uint32_t w = heads * d;
+    if (int rc = check_head_words("el", el, ldel, heads, why)) return rc;
+    if (int rc = check_head_words("er", er, lder, heads, why)) return rc;
+    if (int rc = hsw::check_features("v", v, ldv, w, why)) return rc;
+    if (int rc = hsw::check_features("gy", gy, ldgy, w, why)) return rc;
+    if (int rc = check_lse(lse, ldl, heads, why)) return rc;
+    if (int rc = check_head_words("gel", gel, ldgel, heads, why)) return rc;
+    if (int rc = check_head_words("ger", ger, ldger, heads, why)) return rc;
+    if (int rc = hsw::check_features("gv", gv, ldgv, w, why)) return rc;
+    if (int rc = check_slope(slope, why)) return rc;
+    const hsab::Range in[5] = {{"el", el, lse_reach(num_rows, ldel, heads)}, {"er", er, lse_reach(num_cols, lder, heads)}, {"v", v, hsat::reach(num_cols, ldv, w)},
+                               {"gy", gy, hsat::reach(num_rows, ldgy, w)}, {"lse", lse, lse_reach(num_rows, ldl, heads)}};
+    const hsab::Range out[3] = {{"gel", gel, lse_reach(num_rows, ldgel, heads)}, {"ger", ger, lse_reach(num_cols, ldger, heads)}, {"gv", gv, hsat::reach(num_cols, ldgv, w)}};
+    return hsab::check_overlaps(in, out, why);
+}
+
+// hsgat_backward's: ld = heads * d for V, gY and gV, ld = heads for the five head arrays, no alignment rule
+inline int check_gat_backward_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool backward, const float* el, const float* er, const float* v, const float* gy,
+                                   const float* lse, uint32_t heads, uint32_t d, float slope, const float* gel, const float* ger, const float* gv, std::string& why) {
+    if (int rc = check_backward_flag(backward, why)) return rc;
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    if (!el || !er || !v || !gy || !lse || !gel || !ger || !gv) {
+        why = "null argument";
+        return HS_ERR_BAD_ARG;
+    }
+    if (int rc = check_slope(slope, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4, rh = uint64_t(num_rows) * heads * 4, ch = uint64_t(num_cols) * heads * 4;
+    const hsab::Range in[5] = {{"el", el, rh}, {"er", er, ch}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, rh}};
+    const hsab::Range out[3] = {{"gel", gel, rh}, {"ger", ger, ch}, {"gv", gv, cb}};
+    return hsab::check_overlaps(in, out, why);
 }
 
 }  // namespace hsmh

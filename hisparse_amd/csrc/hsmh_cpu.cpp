@@ -16,6 +16,8 @@
 // The five hsmhd_* calls of include/hisparse_heads_dropout.h run the fp32 loops with a weight w = keep(e, h) ? c : 0 per entry and head from
 // philox.h's generator: forward, l over all entries and the sums over w times the weight; backward, GP becomes w GP and gV takes w P.
 // With drop_p = 0 every w is 1.0 and the loops form the words of the calls without dropout.
+// The four hsgat_* calls of include/hisparse_gat.h run loops of their own (gat_forward_head, gat_backward_head): the score is
+// x = el[row] + er[col], one fp32 add, and t = x > 0 ? x : slope * x, one fp32 multiply; the rest in double as above; gel = A - D B.
 // No dependency beyond the headers and hsmh_common.h: tests/cpp/test_heads_cpu.cpp compiles this file alone under the sanitizers.
 #include <cmath>
 #include <cstring>
@@ -24,6 +26,7 @@
 #include <string>
 #include <vector>
 
+#include "hisparse_gat.h"
 #include "hisparse_heads_bf16.h"
 #include "hisparse_heads_bias.h"
 #include "hisparse_heads_dropout.h"
@@ -186,6 +189,103 @@ void backward(const hsmh_pattern* p, const T* q, uint64_t ldq, const T* k, uint6
         backward_head(p, q + at, ldq, k + at, ldk, v + at, ldv, gy + at, ldgy, lse + h, ldl, d, scale, gq + at, ldgq, gk + at, ldgk, gv + at, ldgv, bias ? bias + h : nullptr, ldb,
                       gbias ? gbias + h : nullptr, ldgb, dr, h);
     }
+}
+
+// ---- include/hisparse_gat.h: one head; el, gel and lse point at the head's word of row 0, er and ger at its word of column 0 ------------
+inline float gat_score(float a, float b) { return a + b; }                                        // x: one fp32 add
+inline float gat_leaky(float x, float slope) { return x > 0.0f ? x : slope * x; }                 // t: one fp32 multiply; x == 0 and NaN take the slope branch
+inline double gat_slope_at(float x, float slope) { return x > 0.0f ? 1.0 : double(slope); }      // torch's leaky_relu derivative, at x == 0 too
+
+void gat_forward_head(const hsmh_pattern* p, const float* el, uint64_t ldel, const float* er, uint64_t lder, const float* v, uint64_t ldv, uint32_t d, float slope, float* y,
+                      uint64_t ldy, float* lse, uint64_t ldl) {
+    const float ninf = -std::numeric_limits<float>::infinity();
+    std::vector<float> t;
+    std::vector<double> acc(d);
+    for (uint32_t r = 0; r < p->num_rows; ++r) {
+        const uint64_t lo = p->indptr[r], hi = p->indptr[r + 1];
+        float* dst = y + uint64_t(r) * ldy;
+        if (lo == hi) {
+            for (uint32_t j = 0; j < d; ++j) dst[j] = 0.0f;
+            if (lse) lse[uint64_t(r) * ldl] = ninf;
+            continue;
+        }
+        const float a = el[uint64_t(r) * ldel];
+        t.resize(hi - lo);
+        float m = ninf;      // one of the t words; a NaN is never the maximum
+        for (uint64_t e = lo; e < hi; ++e) {
+            t[e - lo] = gat_leaky(gat_score(a, er[uint64_t(p->indices[e]) * lder]), slope);
+            m = std::fmax(m, t[e - lo]);
+        }
+        double l = 0.0;
+        acc.assign(d, 0.0);
+        for (uint64_t e = lo; e < hi; ++e) {
+            // a -inf score weighs exactly 0, also while the maximum is -inf itself; a NaN, or +inf under a maximum of +inf, gives NaN
+            const double w = t[e - lo] == ninf ? 0.0 : std::exp(double(t[e - lo]) - double(m));
+            const float* b = v + uint64_t(p->indices[e]) * ldv;
+            l += w;
+            for (uint32_t j = 0; j < d; ++j) acc[j] += w * double(b[j]);
+        }
+        for (uint32_t j = 0; j < d; ++j) dst[j] = float(acc[j] / l);
+        if (lse) lse[uint64_t(r) * ldl] = float(double(m) + std::log(l));
+    }
+}
+
+void gat_backward_head(const hsmh_pattern* p, const float* el, uint64_t ldel, const float* er, uint64_t lder, const float* v, uint64_t ldv, const float* gy, uint64_t ldgy,
+                       const float* lse, uint64_t ldl, uint32_t d, float slope, float* gel, uint64_t ldgel, float* ger, uint64_t ldger, float* gv, uint64_t ldgv) {
+    std::vector<double> w, gp, dx;
+    std::vector<double> sum_r(p->num_cols, 0.0), sum_v(size_t(p->num_cols) * d, 0.0);
+    for (uint32_t r = 0; r < p->num_rows; ++r) {
+        const uint64_t lo = p->indptr[r], hi = p->indptr[r + 1];
+        if (lo == hi) {
+            gel[uint64_t(r) * ldgel] = 0.0f;
+            continue;
+        }
+        const float a = el[uint64_t(r) * ldel];
+        const float* g = gy + uint64_t(r) * ldgy;
+        // a word that is not finite (a dead or bad row of the forward) makes every weight of the row's head NaN
+        const float lw = lse[uint64_t(r) * ldl];
+        const double l = std::isfinite(lw) ? double(lw) : std::numeric_limits<double>::quiet_NaN();
+        w.resize(hi - lo);
+        gp.resize(hi - lo);
+        dx.resize(hi - lo);
+        double dsum = 0.0, asum = 0.0, bsum = 0.0;      // D = sum P GP, A = sum P GP dx, B = sum P dx
+        for (uint64_t e = lo; e < hi; ++e) {
+            const float* c = v + uint64_t(p->indices[e]) * ldv;
+            const float x = gat_score(a, er[uint64_t(p->indices[e]) * lder]);
+            double s = 0.0;
+            for (uint32_t j = 0; j < d; ++j) s += double(g[j] * c[j]);
+            w[e - lo] = std::exp(double(gat_leaky(x, slope)) - l);      // a -inf score under a finite lse weighs exactly 0
+            gp[e - lo] = s;
+            dx[e - lo] = gat_slope_at(x, slope);
+            const double pg = w[e - lo] * s;
+            dsum += pg;
+            asum += pg * dx[e - lo];
+            bsum += w[e - lo] * dx[e - lo];
+        }
+        gel[uint64_t(r) * ldgel] = float(asum - dsum * bsum);
+        for (uint64_t e = lo; e < hi; ++e) {
+            const uint32_t c = p->indices[e];
+            const double pe = w[e - lo];
+            sum_r[c] += (pe * (gp[e - lo] - dsum)) * dx[e - lo];
+            double* to_v = sum_v.data() + size_t(c) * d;
+            for (uint32_t j = 0; j < d; ++j) to_v[j] += pe * double(g[j]);
+        }
+    }
+    for (uint32_t c = 0; c < p->num_cols; ++c) {
+        ger[uint64_t(c) * ldger] = float(sum_r[c]);
+        for (uint32_t j = 0; j < d; ++j) gv[uint64_t(c) * ldgv + j] = float(sum_v[size_t(c) * d + j]);
+    }
+}
+
+void gat_forward(const hsmh_pattern* p, const float* el, uint64_t ldel, const float* er, uint64_t lder, const float* v, uint64_t ldv, uint32_t heads, uint32_t d, float slope, float* y,
+                 uint64_t ldy, float* lse, uint64_t ldl) {
+    for (uint32_t h = 0; h < heads; ++h) gat_forward_head(p, el + h, ldel, er + h, lder, v + h * d, ldv, d, slope, y + h * d, ldy, lse ? lse + h : nullptr, ldl);
+}
+
+void gat_backward(const hsmh_pattern* p, const float* el, uint64_t ldel, const float* er, uint64_t lder, const float* v, uint64_t ldv, const float* gy, uint64_t ldgy, const float* lse,
+                  uint64_t ldl, uint32_t heads, uint32_t d, float slope, float* gel, uint64_t ldgel, float* ger, uint64_t ldger, float* gv, uint64_t ldgv) {
+    for (uint32_t h = 0; h < heads; ++h)
+        gat_backward_head(p, el + h, ldel, er + h, lder, v + h * d, ldv, gy + h * d, ldgy, lse + h, ldl, d, slope, gel + h, ldgel, ger + h, ldger, gv + h * d, ldgv);
 }
 
 }  // namespace
@@ -416,5 +516,48 @@ int hsmhd_backward(hsmh_pattern* p, const float* q, const float* k, const float*
 }
 
 int hsmhd_keep_mask(uint64_t nnz, uint32_t heads, float drop_p, uint64_t seed, uint64_t offset, uint8_t* keep) { return hisparse::hsmh::keep_mask(nnz, heads, drop_p, seed, offset, keep); }
+
+// ---- include/hisparse_gat.h: the same object, additive (GAT) scores from one word per node and head ----------------------------------
+int hsgat_forward_device(hsmh_pattern* p, const float* el_dev, uint64_t ldel, const float* er_dev, uint64_t lder, const float* v_dev, uint64_t ldv, uint32_t heads, uint32_t d,
+                         float slope, float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat_forward(p->num_rows, p->num_cols, p->max_heads, el_dev, ldel, er_dev, lder, v_dev, ldv, heads, d, slope, y_dev, ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    gat_forward(p, el_dev, ldel, er_dev, lder, v_dev, ldv, heads, d, slope, y_dev, ldy, lse_dev, ldl);
+    return HS_OK;
+}
+
+int hsgat_forward(hsmh_pattern* p, const float* el, const float* er, const float* v, uint32_t heads, uint32_t d, float slope, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat_forward_host(p->num_rows, p->num_cols, p->max_heads, el, er, v, heads, d, slope, y, lse, why)) return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    gat_forward(p, el, heads, er, heads, v, w, heads, d, slope, y, w, lse, heads);
+    return HS_OK;
+}
+
+int hsgat_backward_device(hsmh_pattern* p, const float* el_dev, uint64_t ldel, const float* er_dev, uint64_t lder, const float* v_dev, uint64_t ldv, const float* gy_dev, uint64_t ldgy,
+                          const float* lse_dev, uint64_t ldl, uint32_t heads, uint32_t d, float slope, float* gel_dev, uint64_t ldgel, float* ger_dev, uint64_t ldger, float* gv_dev,
+                          uint64_t ldgv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat_backward(p->num_rows, p->num_cols, p->max_heads, p->backward, el_dev, ldel, er_dev, lder, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d,
+                                                    slope, gel_dev, ldgel, ger_dev, ldger, gv_dev, ldgv, why))
+        return fail(p, rc, why);
+    gat_backward(p, el_dev, ldel, er_dev, lder, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, slope, gel_dev, ldgel, ger_dev, ldger, gv_dev, ldgv);
+    return HS_OK;
+}
+
+int hsgat_backward(hsmh_pattern* p, const float* el, const float* er, const float* v, const float* gy, const float* lse, uint32_t heads, uint32_t d, float slope, float* gel,
+                   float* ger, float* gv) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat_backward_host(p->num_rows, p->num_cols, p->max_heads, p->backward, el, er, v, gy, lse, heads, d, slope, gel, ger, gv, why))
+        return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    gat_backward(p, el, heads, er, heads, v, w, gy, w, lse, heads, heads, d, slope, gel, heads, ger, heads, gv, w);
+    return HS_OK;
+}
 
 }  // extern "C"
