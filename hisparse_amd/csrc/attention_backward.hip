@@ -11,6 +11,8 @@
 //     Q[r] and gY[r], reads lse[r] and dsum[r], forms gs = scale p (gp - D_r) and adds gK_j += gs Q_j, gV_j += p gY_j.
 //   Where a group has at least kWideInFlight lanes, lane i of it forms the weight of the trip's entry i and the others fetch it by a
 //   shuffle: one exp per lane and trip.  The groups of a team merge by lane shuffles, a long row's (column's) four wavefronts through LDS.
+// This file owns Trip, gather_dots, weights and store_chunk (a row of any d <= 256: the last chunk may hold fewer than four words), the two
+// kernels and their launchers.  Which row a lane works on (pick, trips_of) and the merges (merge_lanes, merge_waves) are wide_lanes.h's.
 // A row whose lse word is not finite has p = NaN in every entry: NaN in its gQ, its D and in gK and gV of every column it touches.
 // Every output word has one writer: no atomics, no scratch, no matrix engine, no inline assembly.  Arithmetic: the header's ARITHMETIC
 // block -- fp32 products added in double, s rounded once to fp32 and multiplied by scale in fp32, gp kept double, everything after that
@@ -21,60 +23,15 @@
 #include <cstdint>
 
 #include "attention_backward.h"
+#include "wide_lanes.h"
 
 namespace hisparse {
 namespace dev {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace lanes;
 
-constexpr uint32_t kWaves = kWideThreads / 64;
 constexpr uint32_t kSums = 8;      // double sums per lane that cross lanes: a and b of the row side, gK and gV of the column side
-
-__device__ __forceinline__ uint32_t class_of(const WideTable& t, uint64_t w) {
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < kWideClasses; ++k) c += w >= t.first[k] ? 1u : 0u;
-    return c;
-}
-
-// what one lane does in virtual workgroup w: row (column) r with entries lo ... hi, group g of `groups` in a team of `team` lanes
-struct Work {
-    uint32_t c, r, lo, hi, g, groups, team;
-    bool mine;      // false: a team past the end of its class's list runs on with no entries and stores nothing
-};
-
-__device__ __forceinline__ Work pick(const WideTable& tab, uint64_t w, const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ list, uint32_t group) {
-    Work k = {class_of(tab, w), 0u, 0u, 0u, 0u, 0u, 64u, true};
-    if (k.c != 0) {
-        k.team = min(group << (2u * k.c), 64u);
-        const uint64_t slot = (w - tab.first[k.c]) * (kWideThreads / k.team) + threadIdx.x / k.team;
-        k.mine = slot < tab.off[k.c + 1] - tab.off[k.c];
-        if (k.mine) {
-            k.r = list[tab.off[k.c] + slot];
-            k.lo = ptr[k.r];
-            k.hi = ptr[k.r + 1];
-        }
-        k.g = (threadIdx.x & (k.team - 1u)) / group;
-        k.groups = k.team / group;
-    } else {
-        k.r = list[tab.off[0] + (w - tab.first[0])];
-        k.lo = ptr[k.r];
-        k.hi = ptr[k.r + 1];
-        k.g = threadIdx.x / group;
-        k.groups = kWideThreads / group;
-    }
-    return k;
-}
-
-// the trips every lane of the wavefront makes: the most any of its teams needs, so that the shuffles stay convergent
-__device__ __forceinline__ uint32_t trips_of(const Work& k) {
-    const uint32_t per_trip = kWideInFlight * k.groups;
-    uint32_t trips = (k.hi - k.lo + per_trip - 1u) / per_trip;
-#pragma unroll
-    for (uint32_t k2 = 32; k2; k2 >>= 1) trips = max(trips, uint32_t(__shfl_xor(int(trips), int(k2), 64)));
-    return trips;
-}
 
 // One trip of a group: kWideInFlight entries, their gathered chunks and their two dots (the same words in every lane of the group).
 struct Trip {
@@ -129,9 +86,6 @@ __device__ __forceinline__ void gather_dots(Trip& t, const uint32_t* __restrict_
     }
 }
 
-// lse as the weights read it: a word that is not finite (a dead or bad row of the forward) makes every weight of its row NaN
-__device__ __forceinline__ double lse_of(float l) { return __builtin_isfinite(l) ? static_cast<double>(l) : static_cast<double>(__builtin_nanf("")); }
-
 // p[i] = exp(scale * (float)s[i] - lse_of(l[i])): s rounded once, one fp32 multiply, the rest double.  A -inf score under a finite lse weighs
 // exactly 0 (exp(-inf)).  With at least kWideInFlight lanes in a group, lane i forms entry i's weight and the others fetch it.
 __device__ __forceinline__ void weights(double (&p)[kWideInFlight], const double (&s)[kWideInFlight], const float (&l)[kWideInFlight], float scale, uint32_t group) {
@@ -148,30 +102,6 @@ __device__ __forceinline__ void weights(double (&p)[kWideInFlight], const double
         for (uint32_t i = 0; i < kWideInFlight; ++i) p[i] = exp(static_cast<double>(scale * static_cast<float>(s[i])) - lse_of(l[i]));
     }
 }
-static_assert(kWideInFlight == 4, "a trip's weights are dealt to four lanes of a group");
-
-// the sums of the lanes that differ in the bits from ... to/2 of the lane index become one
-__device__ __forceinline__ void merge_lanes(double (&acc)[kSums], uint32_t from, uint32_t to) {
-    for (uint32_t k = from; k < to; k <<= 1) {
-#pragma unroll
-        for (uint32_t j = 0; j < kSums; ++j) acc[j] += __shfl_xor(acc[j], int(k), 64);
-    }
-}
-
-// a long row: the four wavefronts' sums through LDS into wave 0's lanes < group (the others' acc is left as it was); the caller syncs
-// once more before the next use of red
-__device__ __forceinline__ void merge_waves(double (&red)[kWaves][kSums][64], double (&acc)[kSums], uint32_t lane, uint32_t wave, uint32_t group) {
-    if (lane < group) {
-#pragma unroll
-        for (uint32_t j = 0; j < kSums; ++j) red[wave][j][lane] = acc[j];
-    }
-    __syncthreads();
-    if (wave == 0 && lane < group) {
-#pragma unroll
-        for (uint32_t j = 0; j < kSums; ++j) acc[j] = ((red[0][j][lane] + red[1][j][lane]) + red[2][j][lane]) + red[3][j][lane];
-    }
-}
-static_assert(kWaves == 4, "the long rows' merge adds four wavefronts");
 
 // the first `words` (1 ... 4) of a chunk
 __device__ __forceinline__ void store_chunk(float* dst, double x, double y, double z, double w, uint32_t words) {
@@ -314,8 +244,6 @@ __global__ __launch_bounds__(kWideThreads) void attention_backward_cols_kernel(c
     }
 }
 
-dim3 grid_of(const WideSide& s, const WideTable& t) { return dim3(std::min<uint32_t>(t.first[kWideClasses], (s.compute_units ? s.compute_units : 1u) * kWideBlocksPerCu)); }
-
 }  // namespace
 
 hipError_t launch_attention_backward_rows(const WideSide& s, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, const float* gy, uint64_t ldgy,
@@ -323,7 +251,7 @@ hipError_t launch_attention_backward_rows(const WideSide& s, const float* q, uin
     if (d == 0 || d > kWideMaxD) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, d);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;      // a side has at least one row, and an empty row is of class 1
-    hipLaunchKernelGGL(attention_backward_rows_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, d,
+    hipLaunchKernelGGL(attention_backward_rows_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, d,
                        wide_group_lanes(d), scale, gq, ldgq, dsum);
     return hipGetLastError();
 }
@@ -333,7 +261,7 @@ hipError_t launch_attention_backward_cols(const WideSide& s, const float* q, uin
     if (d == 0 || d > kWideMaxD) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, d);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attention_backward_cols_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, dsum, d,
+    hipLaunchKernelGGL(attention_backward_cols_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, dsum, d,
                        wide_group_lanes(d), scale, gk, ldgk, gv, ldgv);
     return hipGetLastError();
 }

@@ -1,8 +1,8 @@
 // gat_attention.hip — include/hisparse_gat.h's three kernels: the graph attention (GAT) step over a CSR pattern, all heads of a call in one
 // pass, forward (ONE launch) and backward (TWO).  The score of an entry is additive, x[e][h] = el[row(e)][h] + er[col(e)][h] and
 // t = LeakyReLU(x): there is no Q, no K and no dot in the forward, and per entry a lane gathers its 16 bytes of V[col(e)] and ONE word of er.
-// The schedule, the Place and Work logic and the merges are heads_attention.hip's, restated here as heads_bias_attention.hip restates them
-// (those files are not touched).  What differs:
+// The schedule, Place and Work, the online softmax State and the merges are wide_lanes.h's, the very definitions heads_attention.hip uses;
+// this file owns `score_of`, `leaky`, `slope_at`, the trip loops written out in its three kernels, and their launchers.  What differs:
 //   Forward: a lane reads its head's el word once per row; per trip the four gathers of V and the four one-word loads of er are issued
 //     before the first use.  The lanes of a head load the same er word, so every lane forms x and t itself: no shuffle inside a head.
 //   Row side of the backward: the row's gY chunk, el word and lse word stay in registers; the lanes of a head add the partial dots of
@@ -20,61 +20,16 @@
 #include <cstdint>
 
 #include "gat_attention.h"
+#include "wide_lanes.h"
 
 namespace hisparse {
 namespace dev {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace lanes;
 
-constexpr uint32_t kWaves = kWideThreads / 64;
 constexpr uint32_t kRowSums = 3;      // row side: D, A and B of this lane's head
 constexpr uint32_t kColSums = 5;      // column side: gV of this lane's chunk (0 ... 3) and ger of its head (4)
-
-__device__ __forceinline__ uint32_t class_of(const WideTable& t, uint64_t w) {
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < kWideClasses; ++k) c += w >= t.first[k] ? 1u : 0u;
-    return c;
-}
-
-// what one lane does in virtual workgroup w: row (column) r with entries lo ... hi, group g of `groups` in a team of `team` lanes
-struct Work {
-    uint32_t c, r, lo, hi, g, groups, team;
-    bool mine;      // false: a team past the end of its class's list runs on with no entries and stores nothing
-};
-
-__device__ __forceinline__ Work pick(const WideTable& tab, uint64_t w, const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ list, uint32_t group) {
-    Work k = {class_of(tab, w), 0u, 0u, 0u, 0u, 0u, 64u, true};
-    if (k.c != 0) {
-        k.team = min(group << (2u * k.c), 64u);
-        const uint64_t slot = (w - tab.first[k.c]) * (kWideThreads / k.team) + threadIdx.x / k.team;
-        k.mine = slot < tab.off[k.c + 1] - tab.off[k.c];
-        if (k.mine) {
-            k.r = list[tab.off[k.c] + slot];
-            k.lo = ptr[k.r];
-            k.hi = ptr[k.r + 1];
-        }
-        k.g = (threadIdx.x & (k.team - 1u)) / group;
-        k.groups = k.team / group;
-    } else {
-        k.r = list[tab.off[0] + (w - tab.first[0])];
-        k.lo = ptr[k.r];
-        k.hi = ptr[k.r + 1];
-        k.g = threadIdx.x / group;
-        k.groups = kWideThreads / group;
-    }
-    return k;
-}
-
-// the trips every lane of the wavefront makes: the most any of its teams needs, so that the shuffles stay convergent
-__device__ __forceinline__ uint32_t trips_of(const Work& k) {
-    const uint32_t per_trip = kWideInFlight * k.groups;
-    uint32_t trips = (k.hi - k.lo + per_trip - 1u) / per_trip;
-#pragma unroll
-    for (uint32_t k2 = 32; k2; k2 >>= 1) trips = max(trips, uint32_t(__shfl_xor(int(trips), int(k2), 64)));
-    return trips;
-}
 
 // x = fl32(a + b): one fp32 add
 __device__ __forceinline__ float score_of(float a, float b) { return __fadd_rn(a, b); }
@@ -83,77 +38,7 @@ __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.0f ?
 // dt / dx as torch's leaky_relu has it, at x == 0 too
 __device__ __forceinline__ double slope_at(float x, float slope) { return x > 0.0f ? 1.0 : static_cast<double>(slope); }
 
-// this lane's place in its group: its 16 bytes of a feature row and the head they belong to
-struct Place {
-    uint32_t at;              // first word of the chunk; 0 for a dead lane
-    uint32_t head;            // 0 for a dead lane
-    uint32_t head_lanes;      // d / 4
-    bool live, lead;          // lead: the first lane of a live head, which stores the head's words of lse, D, gel or ger
-};
-
-__device__ __forceinline__ Place place_of(uint32_t group, uint32_t heads, uint32_t d) {
-    const uint32_t chunk = threadIdx.x & (group - 1u);
-    Place p;
-    p.head_lanes = d >> 2;
-    p.live = chunk * 4u < heads * d;
-    p.at = p.live ? chunk * 4u : 0u;
-    p.head = p.live ? chunk >> (__builtin_ctz(d) - 2) : 0u;
-    p.lead = p.live && (chunk & (p.head_lanes - 1u)) == 0u;
-    return p;
-}
-
-// the four fp32 products of a chunk added in double
-__device__ __forceinline__ double dot4(f32x4 a, f32x4 b) {
-    return ((static_cast<double>(a.x * b.x) + static_cast<double>(a.y * b.y)) + static_cast<double>(a.z * b.z)) + static_cast<double>(a.w * b.w);
-}
-
-__device__ __forceinline__ void store4(float* dst, double x, double y, double z, double w) {
-    f32x4 v = {static_cast<float>(x), static_cast<float>(y), static_cast<float>(z), static_cast<float>(w)};
-    *reinterpret_cast<f32x4*>(dst) = v;
-}
-
-static_assert(kWideInFlight == 4, "a trip is four entries");
-static_assert(kWaves == 4, "the long rows' merge adds four wavefronts");
-
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------
-struct Sum4 {
-    double a, b, c, d;
-};
-
-// the online softmax state of one lane: its head's m and l, and the four sums of its chunk
-struct State {
-    float m;      // one of the t words, or -inf
-    double l;
-    Sum4 acc;
-};
-
-// NaN is never the maximum (fmaxf returns the other operand)
-__device__ __forceinline__ void raise_to(State& s, float m_new) {
-    if (m_new != s.m) {      // m_new > s.m: exp(-inf - finite) = 0 for a state that is still empty
-        const double f = exp(static_cast<double>(s.m) - static_cast<double>(m_new));
-        s.l *= f;
-        s.acc.a *= f;
-        s.acc.b *= f;
-        s.acc.c *= f;
-        s.acc.d *= f;
-        s.m = m_new;
-    }
-}
-
-// the states of the lanes that differ in the bits from ... to/2 of the lane index become one: the maximum first, then the rescaled sums
-__device__ __forceinline__ void merge_states(State& s, uint32_t from, uint32_t to) {
-    float m = s.m;
-    for (uint32_t k = from; k < to; k <<= 1) m = fmaxf(m, __shfl_xor(m, int(k), 64));
-    raise_to(s, m);
-    for (uint32_t k = from; k < to; k <<= 1) {
-        s.l += __shfl_xor(s.l, int(k), 64);
-        s.acc.a += __shfl_xor(s.acc.a, int(k), 64);
-        s.acc.b += __shfl_xor(s.acc.b, int(k), 64);
-        s.acc.c += __shfl_xor(s.acc.c, int(k), 64);
-        s.acc.d += __shfl_xor(s.acc.d, int(k), 64);
-    }
-}
-
 __global__ __launch_bounds__(kWideThreads) void gat_forward_kernel(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ list, WideTable tab,
                                                                   const float* __restrict__ el, uint64_t ldel, const float* __restrict__ er, uint64_t lder,
                                                                   const float* __restrict__ v, uint64_t ldv, uint32_t heads, uint32_t d, uint32_t group, float slope,
@@ -247,33 +132,6 @@ __global__ __launch_bounds__(kWideThreads) void gat_forward_kernel(const uint32_
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------------------
-// lse as the weights read it: a word that is not finite (a dead or bad row of the forward) makes every weight of its row and head NaN
-__device__ __forceinline__ double lse_of(float l) { return __builtin_isfinite(l) ? static_cast<double>(l) : static_cast<double>(__builtin_nanf("")); }
-
-// the sums of the lanes that differ in the bits from ... to/2 of the lane index become one
-template <uint32_t kN>
-__device__ __forceinline__ void merge_lanes(double (&acc)[kN], uint32_t from, uint32_t to) {
-    for (uint32_t k = from; k < to; k <<= 1) {
-#pragma unroll
-        for (uint32_t j = 0; j < kN; ++j) acc[j] += __shfl_xor(acc[j], int(k), 64);
-    }
-}
-
-// a long row: the four wavefronts' sums through LDS into wave 0's lanes < group (the others' acc is left as it was); the caller syncs
-// once more before the next use of red
-template <uint32_t kN>
-__device__ __forceinline__ void merge_waves(double (&red)[kWaves][kN][64], double (&acc)[kN], uint32_t lane, uint32_t wave, uint32_t group) {
-    if (lane < group) {
-#pragma unroll
-        for (uint32_t j = 0; j < kN; ++j) red[wave][j][lane] = acc[j];
-    }
-    __syncthreads();
-    if (wave == 0 && lane < group) {
-#pragma unroll
-        for (uint32_t j = 0; j < kN; ++j) acc[j] = ((red[0][j][lane] + red[1][j][lane]) + red[2][j][lane]) + red[3][j][lane];
-    }
-}
-
 __global__ __launch_bounds__(kWideThreads) void gat_backward_rows_kernel(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ list,
                                                                         WideTable tab, const float* __restrict__ el, uint64_t ldel, const float* __restrict__ er, uint64_t lder,
                                                                         const float* __restrict__ v, uint64_t ldv, const float* __restrict__ gy, uint64_t ldgy,
@@ -428,11 +286,6 @@ __global__ __launch_bounds__(kWideThreads) void gat_backward_cols_kernel(const u
     }
 }
 
-dim3 grid_of(const WideSide& s, const WideTable& t) { return dim3(std::min<uint32_t>(t.first[kWideClasses], (s.compute_units ? s.compute_units : 1u) * kWideBlocksPerCu)); }
-
-// d a power of two from 4, heads * d at most kWideMaxD: what place_of relies on
-bool shape_ok(uint32_t heads, uint32_t d) { return d >= 4u && (d & (d - 1u)) == 0u && heads >= 1u && uint64_t(heads) * d <= kWideMaxD; }
-
 }  // namespace
 
 hipError_t launch_gat_forward(const WideSide& s, const float* el, uint64_t ldel, const float* er, uint64_t lder, const float* v, uint64_t ldv, uint32_t heads, uint32_t d, float slope,
@@ -440,7 +293,7 @@ hipError_t launch_gat_forward(const WideSide& s, const float* el, uint64_t ldel,
     if (!shape_ok(heads, d) || ldel < heads || lder < heads || (lse && ldl < heads)) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, heads * d);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;      // a side has at least one row, and an empty row is of class 1
-    hipLaunchKernelGGL(gat_forward_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, el, ldel, er, lder, v, ldv, heads, d, wide_group_lanes(heads * d), slope, y,
+    hipLaunchKernelGGL(gat_forward_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, el, ldel, er, lder, v, ldv, heads, d, wide_group_lanes(heads * d), slope, y,
                        ldy, lse, ldl);
     return hipGetLastError();
 }
@@ -451,7 +304,7 @@ hipError_t launch_gat_backward_rows(const WideSide& s, const float* el, uint64_t
     if (!shape_ok(heads, d) || ldel < heads || lder < heads || ldl < heads || ldgel < heads || ldd < heads) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, heads * d);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gat_backward_rows_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, el, ldel, er, lder, v, ldv, gy, ldgy, lse, ldl, heads, d,
+    hipLaunchKernelGGL(gat_backward_rows_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, el, ldel, er, lder, v, ldv, gy, ldgy, lse, ldl, heads, d,
                        wide_group_lanes(heads * d), slope, gel, ldgel, dsum, ldd);
     return hipGetLastError();
 }
@@ -462,7 +315,7 @@ hipError_t launch_gat_backward_cols(const WideSide& s, const float* el, uint64_t
     if (!shape_ok(heads, d) || ldel < heads || lder < heads || ldl < heads || ldger < heads || ldd < heads) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, heads * d);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gat_backward_cols_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, el, ldel, er, lder, v, ldv, gy, ldgy, lse, ldl, dsum, ldd, heads, d,
+    hipLaunchKernelGGL(gat_backward_cols_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, el, ldel, er, lder, v, ldv, gy, ldgy, lse, ldl, dsum, ldd, heads, d,
                        wide_group_lanes(heads * d), slope, ger, ldger, gv, ldgv);
     return hipGetLastError();
 }

@@ -1,10 +1,11 @@
 // heads16_attention.hip — include/hisparse_heads_bf16.h's three kernels: multi-head attention over a CSR pattern, forward and backward,
 // with ROW-MAJOR bf16 operands stored [index][head][feature] (heads * d <= 512 elements, d a power of two from 8) and no per-entry array.
 // ONE launch forward, TWO backward.  They are heads_attention.hip's kernels with a lane owning one 16-byte chunk of EIGHT bf16 elements
-// where a lane there owns four fp32 words; that file stays as it is and its helpers are file-local, so the schedule helpers (class_of, pick,
-// trips_of) are restated here word for word.  The schedule is wide_products.h's, unchanged, taken at the row's size in 16-byte chunks: the
-// launchers pass heads * d / 2 where the fp32 launchers pass heads * d, so the group of a row is half as wide and a wavefront holds twice
-// the entries in flight per trip.
+// where a lane there owns four fp32 words.  Which row a lane works on (pick, trips_of), its Place (place_of<8>) and the merges of plain
+// sums are wide_lanes.h's, the definitions the fp32 files use; this file owns the bf16 words (F8, widen, dot8, store8), an eight-sum
+// State with its raise_to and merge_states, its trip loops, the three kernels and their launchers.  The schedule is wide_products.h's,
+// unchanged, taken at the row's size in 16-byte chunks: the launchers pass heads * d / 2 where the fp32 launchers pass heads * d, so the
+// group of a row is half as wide and a wavefront holds twice the entries in flight per trip.
 //   head_lanes = d / 8, head = chunk / head_lanes.  The shuffles of a dot run over k < head_lanes, so every lane of a head holds the
 //     head's s (and gp), and every lane carries its own head's m and l (forward) or D (backward).
 //   Where a head has at least kWideInFlight lanes (d >= 32), lane i of it forms the weight of the trip's entry i and the others fetch
@@ -23,6 +24,7 @@
 #include <cstdint>
 
 #include "heads16_attention.h"
+#include "wide_lanes.h"
 
 namespace hisparse {
 namespace dev {
@@ -31,75 +33,21 @@ namespace {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));      // a chunk: eight bf16 elements, element 2 i in the low half of dword i
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr uint32_t kWaves = kWideThreads / 64;
+// named one by one: State, raise_to and merge_states below are this file's own, under the names wide_lanes.h has for the fp32 ones
+using lanes::grid_of;
+using lanes::kWaves;
+using lanes::lse_of;
+using lanes::merge_lanes;
+using lanes::merge_waves;
+using lanes::pick;
+using lanes::Place;
+using lanes::place_of;
+using lanes::shape_ok;
+using lanes::trips_of;
+using lanes::Work;
+
 constexpr uint32_t kChunk = 8;               // elements per lane
 constexpr uint32_t kSums = 2 * kChunk;       // backward: double sums per lane that cross lanes, a and b of the row side, gK and gV of the column side
-
-__device__ __forceinline__ uint32_t class_of(const WideTable& t, uint64_t w) {
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < kWideClasses; ++k) c += w >= t.first[k] ? 1u : 0u;
-    return c;
-}
-
-// what one lane does in virtual workgroup w: row (column) r with entries lo ... hi, group g of `groups` in a team of `team` lanes
-struct Work {
-    uint32_t c, r, lo, hi, g, groups, team;
-    bool mine;      // false: a team past the end of its class's list runs on with no entries and stores nothing
-};
-
-__device__ __forceinline__ Work pick(const WideTable& tab, uint64_t w, const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ list, uint32_t group) {
-    Work k = {class_of(tab, w), 0u, 0u, 0u, 0u, 0u, 64u, true};
-    if (k.c != 0) {
-        k.team = min(group << (2u * k.c), 64u);
-        const uint64_t slot = (w - tab.first[k.c]) * (kWideThreads / k.team) + threadIdx.x / k.team;
-        k.mine = slot < tab.off[k.c + 1] - tab.off[k.c];
-        if (k.mine) {
-            k.r = list[tab.off[k.c] + slot];
-            k.lo = ptr[k.r];
-            k.hi = ptr[k.r + 1];
-        }
-        k.g = (threadIdx.x & (k.team - 1u)) / group;
-        k.groups = k.team / group;
-    } else {
-        k.r = list[tab.off[0] + (w - tab.first[0])];
-        k.lo = ptr[k.r];
-        k.hi = ptr[k.r + 1];
-        k.g = threadIdx.x / group;
-        k.groups = kWideThreads / group;
-    }
-    return k;
-}
-
-// the trips every lane of the wavefront makes: the most any of its teams needs, so that the shuffles stay convergent
-__device__ __forceinline__ uint32_t trips_of(const Work& k) {
-    const uint32_t per_trip = kWideInFlight * k.groups;
-    uint32_t trips = (k.hi - k.lo + per_trip - 1u) / per_trip;
-#pragma unroll
-    for (uint32_t k2 = 32; k2; k2 >>= 1) trips = max(trips, uint32_t(__shfl_xor(int(trips), int(k2), 64)));
-    return trips;
-}
-
-// this lane's place in its group: its 16 bytes of a feature row and the head they belong to
-struct Place {
-    uint32_t at;              // first element of the chunk; 0 for a dead lane
-    uint32_t head;            // 0 for a dead lane
-    uint32_t head_lanes;      // d / 8
-    int first;                // the first lane of this lane's head in the wavefront
-    bool live, lead;          // lead: the first lane of a live head, which stores the head's lse or D word
-};
-
-__device__ __forceinline__ Place place_of(uint32_t group, uint32_t heads, uint32_t d) {
-    const uint32_t chunk = threadIdx.x & (group - 1u);
-    Place p;
-    p.head_lanes = d >> 3;
-    p.live = chunk * kChunk < heads * d;
-    p.at = p.live ? chunk * kChunk : 0u;
-    p.head = p.live ? chunk >> (__builtin_ctz(d) - 3) : 0u;
-    p.first = int(threadIdx.x & 63u & ~(p.head_lanes - 1u));
-    p.lead = p.live && (chunk & (p.head_lanes - 1u)) == 0u;
-    return p;
-}
 
 __device__ __forceinline__ u32x4 load_chunk(const uint16_t* p) { return *reinterpret_cast<const u32x4*>(p); }
 
@@ -141,11 +89,9 @@ __device__ __forceinline__ void store_zeros(uint16_t* dst) {
     *reinterpret_cast<u32x4*>(dst) = z;
 }
 
-static_assert(kWideInFlight == 4, "a trip's weights are dealt to four lanes of a head");
-static_assert(kWaves == 4, "the long rows' merge adds four wavefronts");
-
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------
-// the online softmax state of one lane: its head's m and l, and the eight sums of its chunk
+// the online softmax state of one lane: its head's m and l, and the eight sums of its chunk.  An array of 8, defined here: one State<N>
+// template shared with the fp32 files (four named sums) reorders the shuffles of their merge, and their device code must not move.
 struct State {
     float m;      // one of the t words, or -inf
     double l;
@@ -240,7 +186,7 @@ __global__ __launch_bounds__(kWideThreads) void heads16_forward_kernel(const uin
     __shared__ double red[kWaves][kChunk][64];
     __shared__ double red_l[kWaves][64];      // per lane: a lane's l and m are its head's
     __shared__ float red_m[kWaves][64];
-    const Place pl = place_of(group, heads, d);
+    const Place pl = place_of<kChunk>(group, heads, d);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint64_t w = blockIdx.x; w < tab.first[kWideClasses]; w += gridDim.x) {
         const Work wk = pick(tab, w, ptr, list, group);
@@ -340,9 +286,6 @@ __device__ __forceinline__ void gather_dots(Trip& t, const uint32_t* __restrict_
     }
 }
 
-// lse as the weights read it: a word that is not finite (a dead or bad row of the forward) makes every weight of its row and head NaN
-__device__ __forceinline__ double lse_of(float l) { return __builtin_isfinite(l) ? static_cast<double>(l) : static_cast<double>(__builtin_nanf("")); }
-
 // p[i] = exp(scale * (float)s[i] - lse_of(l[i])): s rounded once, one fp32 multiply, the rest double.  A -inf score under a finite lse weighs
 // exactly 0 (exp(-inf)).  With at least kWideInFlight lanes in a head, lane i of it forms entry i's weight and the others fetch it.
 __device__ __forceinline__ void weights(double (&p)[kWideInFlight], const double (&s)[kWideInFlight], const float (&l)[kWideInFlight], float scale, const Place& pl) {
@@ -356,28 +299,6 @@ __device__ __forceinline__ void weights(double (&p)[kWideInFlight], const double
     } else {
 #pragma unroll
         for (uint32_t i = 0; i < kWideInFlight; ++i) p[i] = exp(static_cast<double>(scale * static_cast<float>(s[i])) - lse_of(l[i]));
-    }
-}
-
-// the sums of the lanes that differ in the bits from ... to/2 of the lane index become one
-__device__ __forceinline__ void merge_lanes(double (&acc)[kSums], uint32_t from, uint32_t to) {
-    for (uint32_t k = from; k < to; k <<= 1) {
-#pragma unroll
-        for (uint32_t j = 0; j < kSums; ++j) acc[j] += __shfl_xor(acc[j], int(k), 64);
-    }
-}
-
-// a long row: the four wavefronts' sums through LDS into wave 0's lanes < group (the others' acc is left as it was); the caller syncs
-// once more before the next use of red
-__device__ __forceinline__ void merge_waves(double (&red)[kWaves][kSums][64], double (&acc)[kSums], uint32_t lane, uint32_t wave, uint32_t group) {
-    if (lane < group) {
-#pragma unroll
-        for (uint32_t j = 0; j < kSums; ++j) red[wave][j][lane] = acc[j];
-    }
-    __syncthreads();
-    if (wave == 0 && lane < group) {
-#pragma unroll
-        for (uint32_t j = 0; j < kSums; ++j) acc[j] = ((red[0][j][lane] + red[1][j][lane]) + red[2][j][lane]) + red[3][j][lane];
     }
 }
 
@@ -396,7 +317,7 @@ __global__ __launch_bounds__(kWideThreads) void heads16_backward_rows_kernel(con
                                                                             uint16_t* __restrict__ gq, uint64_t ldgq, double* __restrict__ dsum, uint64_t ldd) {
     __shared__ double red[kWaves][kSums][64];
     __shared__ double red_d[kWaves][64];      // per lane: a lane's D is its head's
-    const Place pl = place_of(group, heads, d);
+    const Place pl = place_of<kChunk>(group, heads, d);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const double sc = static_cast<double>(scale);
     for (uint64_t w = blockIdx.x; w < tab.first[kWideClasses]; w += gridDim.x) {
@@ -461,7 +382,7 @@ __global__ __launch_bounds__(kWideThreads) void heads16_backward_cols_kernel(con
                                                                             uint32_t d, uint32_t group, float scale, uint16_t* __restrict__ gk, uint64_t ldgk, uint16_t* __restrict__ gv,
                                                                             uint64_t ldgv) {
     __shared__ double red[kWaves][kSums][64];
-    const Place pl = place_of(group, heads, d);
+    const Place pl = place_of<kChunk>(group, heads, d);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const double sc = static_cast<double>(scale);
     for (uint64_t w = blockIdx.x; w < tab.first[kWideClasses]; w += gridDim.x) {
@@ -507,19 +428,14 @@ __global__ __launch_bounds__(kWideThreads) void heads16_backward_cols_kernel(con
     }
 }
 
-dim3 grid_of(const WideSide& s, const WideTable& t) { return dim3(std::min<uint32_t>(t.first[kWideClasses], (s.compute_units ? s.compute_units : 1u) * kWideBlocksPerCu)); }
-
-// d a power of two from 8, heads * d / 2 at most kWideMaxD (a row is at most 64 chunks): what place_of relies on
-bool shape_ok(uint32_t heads, uint32_t d) { return d >= kChunk && (d & (d - 1u)) == 0u && heads >= 1u && uint64_t(heads) * d <= 2u * kWideMaxD; }
-
 }  // namespace
 
 hipError_t launch_heads16_forward(const WideSide& s, const uint16_t* q, uint64_t ldq, const uint16_t* k, uint64_t ldk, const uint16_t* v, uint64_t ldv, uint32_t heads, uint32_t d,
                                   float scale, uint16_t* y, uint64_t ldy, float* lse, uint64_t ldl, hipStream_t stream) {
-    if (!shape_ok(heads, d)) return hipErrorInvalidValue;
+    if (!shape_ok(heads, d, kChunk)) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, heads * d / 2);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;      // a side has at least one row, and an empty row is of class 1
-    hipLaunchKernelGGL(heads16_forward_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, heads, d, wide_group_lanes(heads * d / 2),
+    hipLaunchKernelGGL(heads16_forward_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, heads, d, wide_group_lanes(heads * d / 2),
                        scale, y, ldy, lse, ldl);
     return hipGetLastError();
 }
@@ -527,10 +443,10 @@ hipError_t launch_heads16_forward(const WideSide& s, const uint16_t* q, uint64_t
 hipError_t launch_heads16_backward_rows(const WideSide& s, const uint16_t* q, uint64_t ldq, const uint16_t* k, uint64_t ldk, const uint16_t* v, uint64_t ldv, const uint16_t* gy,
                                         uint64_t ldgy, const float* lse, uint64_t ldl, uint32_t heads, uint32_t d, float scale, uint16_t* gq, uint64_t ldgq, double* dsum, uint64_t ldd,
                                         hipStream_t stream) {
-    if (!shape_ok(heads, d) || ldd < heads) return hipErrorInvalidValue;
+    if (!shape_ok(heads, d, kChunk) || ldd < heads) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, heads * d / 2);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(heads16_backward_rows_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, heads, d,
+    hipLaunchKernelGGL(heads16_backward_rows_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, heads, d,
                        wide_group_lanes(heads * d / 2), scale, gq, ldgq, dsum, ldd);
     return hipGetLastError();
 }
@@ -538,10 +454,10 @@ hipError_t launch_heads16_backward_rows(const WideSide& s, const uint16_t* q, ui
 hipError_t launch_heads16_backward_cols(const WideSide& s, const uint16_t* q, uint64_t ldq, const uint16_t* k, uint64_t ldk, const uint16_t* v, uint64_t ldv, const uint16_t* gy,
                                         uint64_t ldgy, const float* lse, uint64_t ldl, const double* dsum, uint64_t ldd, uint32_t heads, uint32_t d, float scale, uint16_t* gk,
                                         uint64_t ldgk, uint16_t* gv, uint64_t ldgv, hipStream_t stream) {
-    if (!shape_ok(heads, d) || ldd < heads) return hipErrorInvalidValue;
+    if (!shape_ok(heads, d, kChunk) || ldd < heads) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, heads * d / 2);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(heads16_backward_cols_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, dsum, ldd, heads,
+    hipLaunchKernelGGL(heads16_backward_cols_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, dsum, ldd, heads,
                        d, wide_group_lanes(heads * d / 2), scale, gk, ldgk, gv, ldgv);
     return hipGetLastError();
 }

@@ -3,8 +3,10 @@
 // with or without the per-entry, per-head bias (a wave-uniform branch: without one no bias word is read and t = fl32(scale * s), the plain
 // calls' score).  No mask is stored or read: keep(e, h) is recomputed wherever it is needed from the counter-based generator of philox.h,
 // keyed by the call's seed, offset, the entry's index e IN THE CALLER'S CSR ORDER and the head.
-// The schedule, the Place and Work logic, the dots inside a head, the dealing of a trip's weights and of its bias words, and the merges
-// are heads_bias_attention.hip's, restated here as that file restates heads_attention.hip's (neither is touched).  What is new:
+// The schedule, Place and Work, the online softmax State and the merges are wide_lanes.h's, the very definitions heads_attention.hip and
+// heads_bias_attention.hip use; the dots inside a head and the dealing of a trip's weights and of its bias words follow the latter's trip
+// loops.  This file owns its trip loops (attend_entries; Trip, gather_dots, weights), `score`, `keeps`, the three kernels and their
+// launchers.  What is new:
 //   Forward and row side know the entry's index directly; the column side takes it from the map word perm[e'], which it streams anyway.
 //   Where a head has at least kWideInFlight lanes (d >= 16) lane i of each four draws the Philox words of the trip's entry i alone, one
 //     generator call per lane and trip, and the keep bits reach the head's lanes through ONE ballot of the wavefront: bit first + i is the
@@ -24,106 +26,21 @@
 #include <cstdint>
 
 #include "heads_dropout_attention.h"
+#include "wide_lanes.h"
 
 namespace hisparse {
 namespace dev {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace lanes;
 
-constexpr uint32_t kWaves = kWideThreads / 64;
 constexpr uint32_t kSums = 8;      // backward: double sums per lane that cross lanes, a and b of the row side, gK and gV of the column side
-
-__device__ __forceinline__ uint32_t class_of(const WideTable& t, uint64_t w) {
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < kWideClasses; ++k) c += w >= t.first[k] ? 1u : 0u;
-    return c;
-}
-
-// what one lane does in virtual workgroup w: row (column) r with entries lo ... hi, group g of `groups` in a team of `team` lanes
-struct Work {
-    uint32_t c, r, lo, hi, g, groups, team;
-    bool mine;      // false: a team past the end of its class's list runs on with no entries and stores nothing
-};
-
-__device__ __forceinline__ Work pick(const WideTable& tab, uint64_t w, const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ list, uint32_t group) {
-    Work k = {class_of(tab, w), 0u, 0u, 0u, 0u, 0u, 64u, true};
-    if (k.c != 0) {
-        k.team = min(group << (2u * k.c), 64u);
-        const uint64_t slot = (w - tab.first[k.c]) * (kWideThreads / k.team) + threadIdx.x / k.team;
-        k.mine = slot < tab.off[k.c + 1] - tab.off[k.c];
-        if (k.mine) {
-            k.r = list[tab.off[k.c] + slot];
-            k.lo = ptr[k.r];
-            k.hi = ptr[k.r + 1];
-        }
-        k.g = (threadIdx.x & (k.team - 1u)) / group;
-        k.groups = k.team / group;
-    } else {
-        k.r = list[tab.off[0] + (w - tab.first[0])];
-        k.lo = ptr[k.r];
-        k.hi = ptr[k.r + 1];
-        k.g = threadIdx.x / group;
-        k.groups = kWideThreads / group;
-    }
-    return k;
-}
-
-// the trips every lane of the wavefront makes: the most any of its teams needs, so that the shuffles and the ballot stay convergent
-__device__ __forceinline__ uint32_t trips_of(const Work& k) {
-    const uint32_t per_trip = kWideInFlight * k.groups;
-    uint32_t trips = (k.hi - k.lo + per_trip - 1u) / per_trip;
-#pragma unroll
-    for (uint32_t k2 = 32; k2; k2 >>= 1) trips = max(trips, uint32_t(__shfl_xor(int(trips), int(k2), 64)));
-    return trips;
-}
 
 // t = fl32(fl32(scale * s) + b) with a bias: one fp32 multiply, then one fp32 add; t = fl32(scale * s) without
 __device__ __forceinline__ float score(float scale, double s, float b, bool has_bias) {
     const float t = __fmul_rn(scale, static_cast<float>(s));
     return has_bias ? __fadd_rn(t, b) : t;
 }
-
-// entry i's word of a trip's four, for i that is not known at compile time (no indexed array: that would be scratch)
-template <typename T>
-__device__ __forceinline__ T pick4(const T (&a)[kWideInFlight], uint32_t i) { return i == 0u ? a[0] : i == 1u ? a[1] : i == 2u ? a[2] : a[3]; }
-
-// this lane's place in its group: its 16 bytes of a feature row and the head they belong to
-struct Place {
-    uint32_t at;              // first word of the chunk; 0 for a dead lane
-    uint32_t head;            // 0 for a dead lane
-    uint32_t head_lanes;      // d / 4
-    int first;                // the first lane of this lane's head in the wavefront
-    bool live, lead;          // lead: the first lane of a live head, which stores the head's lse or D word
-    bool deals;               // one of the first kWideInFlight lanes of a live head of at least that many lanes: lane i of them stores entry i's gbias word
-};
-
-__device__ __forceinline__ Place place_of(uint32_t group, uint32_t heads, uint32_t d) {
-    const uint32_t chunk = threadIdx.x & (group - 1u);
-    Place p;
-    p.head_lanes = d >> 2;
-    p.live = chunk * 4u < heads * d;
-    p.at = p.live ? chunk * 4u : 0u;
-    p.head = p.live ? chunk >> (__builtin_ctz(d) - 2) : 0u;
-    p.first = int(threadIdx.x & 63u & ~(p.head_lanes - 1u));
-    p.lead = p.live && (chunk & (p.head_lanes - 1u)) == 0u;
-    p.deals = p.live && p.head_lanes >= kWideInFlight && (chunk & (p.head_lanes - 1u)) < kWideInFlight;
-    return p;
-}
-
-// the four fp32 products of a chunk added in double
-__device__ __forceinline__ double dot4(f32x4 a, f32x4 b) {
-    return ((static_cast<double>(a.x * b.x) + static_cast<double>(a.y * b.y)) + static_cast<double>(a.z * b.z)) + static_cast<double>(a.w * b.w);
-}
-
-__device__ __forceinline__ void store4(float* dst, double x, double y, double z, double w) {
-    f32x4 v = {static_cast<float>(x), static_cast<float>(y), static_cast<float>(z), static_cast<float>(w)};
-    *reinterpret_cast<f32x4*>(dst) = v;
-}
-
-static_assert(kWideInFlight == 4, "a trip's weights and draws are dealt to four lanes of a head");
-static_assert(kWaves == 4, "the long rows' merge adds four wavefronts");
 
 // The keep decisions of a trip's four entries for this lane's head.  ent[i] is entry i's index in the caller's CSR order and entm the one
 // of the entry this lane deals (lane i of each four: entry i); an entry past the end carries index 0 or an index past the end, its draw
@@ -141,47 +58,9 @@ __device__ __forceinline__ void keeps(bool (&kp)[kWideInFlight], const philox::D
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------
-struct Sum4 {
-    double a, b, c, d;
-};
-
-// the online softmax state of one lane: its head's m and l (over all entries), and the four sums of its chunk (over the kept ones)
-struct State {
-    float m;      // one of the t words, or -inf
-    double l;
-    Sum4 acc;
-};
-
-// NaN is never the maximum (fmaxf returns the other operand)
-__device__ __forceinline__ void raise_to(State& s, float m_new) {
-    if (m_new != s.m) {      // m_new > s.m: exp(-inf - finite) = 0 for a state that is still empty
-        const double f = exp(static_cast<double>(s.m) - static_cast<double>(m_new));
-        s.l *= f;
-        s.acc.a *= f;
-        s.acc.b *= f;
-        s.acc.c *= f;
-        s.acc.d *= f;
-        s.m = m_new;
-    }
-}
-
-// the states of the lanes that differ in the bits from ... to/2 of the lane index become one: the maximum first, then the rescaled sums
-__device__ __forceinline__ void merge_states(State& s, uint32_t from, uint32_t to) {
-    float m = s.m;
-    for (uint32_t k = from; k < to; k <<= 1) m = fmaxf(m, __shfl_xor(m, int(k), 64));
-    raise_to(s, m);
-    for (uint32_t k = from; k < to; k <<= 1) {
-        s.l += __shfl_xor(s.l, int(k), 64);
-        s.acc.a += __shfl_xor(s.acc.a, int(k), 64);
-        s.acc.b += __shfl_xor(s.acc.b, int(k), 64);
-        s.acc.c += __shfl_xor(s.acc.c, int(k), 64);
-        s.acc.d += __shfl_xor(s.acc.d, int(k), 64);
-    }
-}
-
-// One row's entries lo + g, lo + g + groups, ... through this lane's state.  Every lane of the wavefront makes `trips` trips; an entry
-// past the end gathers row 0 of K and V (in bounds, in the cache) without reading idx or bias, scores -inf and is not added.  bias_head =
-// bias + this lane's head (never dereferenced without a bias).
+// One row's entries lo + g, lo + g + groups, ... through this lane's state: m and l over all entries, the four sums over the kept ones.
+// Every lane of the wavefront makes `trips` trips; an entry past the end gathers row 0 of K and V (in bounds, in the cache) without reading
+// idx or bias, scores -inf and is not added.  bias_head = bias + this lane's head (never dereferenced without a bias).
 __device__ __forceinline__ void attend_entries(State& st, const uint32_t* __restrict__ idx, f32x4 qv, const Place& pl, const float* __restrict__ k_chunk, uint64_t ldk,
                                                const float* __restrict__ v_chunk, uint64_t ldv, const float* __restrict__ bias_head, uint64_t ldb, float scale,
                                                const philox::Dropout& dr, const Work& wk, uint32_t trips) {
@@ -394,9 +273,6 @@ __device__ __forceinline__ void gather_dots(Trip& t, const uint32_t* __restrict_
     }
 }
 
-// lse as the weights read it: a word that is not finite (a dead or bad row of the forward) makes every weight of its row and head NaN
-__device__ __forceinline__ double lse_of(float l) { return __builtin_isfinite(l) ? static_cast<double>(l) : static_cast<double>(__builtin_nanf("")); }
-
 // p[i] = exp(t[i] - lse_of(l[i])), the weight WITHOUT dropout, with t[i] the score as score() forms it, the rest double.  A -inf score
 // under a finite lse weighs exactly 0 (exp(-inf)).  With at least kWideInFlight lanes in a head, lane i of it forms entry i's weight and
 // the others fetch it.
@@ -412,28 +288,6 @@ __device__ __forceinline__ void weights(double (&p)[kWideInFlight], const double
     } else {
 #pragma unroll
         for (uint32_t i = 0; i < kWideInFlight; ++i) p[i] = exp(static_cast<double>(score(scale, s[i], b[i], has_bias)) - lse_of(l[i]));
-    }
-}
-
-// the sums of the lanes that differ in the bits from ... to/2 of the lane index become one
-__device__ __forceinline__ void merge_lanes(double (&acc)[kSums], uint32_t from, uint32_t to) {
-    for (uint32_t k = from; k < to; k <<= 1) {
-#pragma unroll
-        for (uint32_t j = 0; j < kSums; ++j) acc[j] += __shfl_xor(acc[j], int(k), 64);
-    }
-}
-
-// a long row: the four wavefronts' sums through LDS into wave 0's lanes < group (the others' acc is left as it was); the caller syncs
-// once more before the next use of red
-__device__ __forceinline__ void merge_waves(double (&red)[kWaves][kSums][64], double (&acc)[kSums], uint32_t lane, uint32_t wave, uint32_t group) {
-    if (lane < group) {
-#pragma unroll
-        for (uint32_t j = 0; j < kSums; ++j) red[wave][j][lane] = acc[j];
-    }
-    __syncthreads();
-    if (wave == 0 && lane < group) {
-#pragma unroll
-        for (uint32_t j = 0; j < kSums; ++j) acc[j] = ((red[0][j][lane] + red[1][j][lane]) + red[2][j][lane]) + red[3][j][lane];
     }
 }
 
@@ -570,11 +424,6 @@ __global__ __launch_bounds__(kWideThreads) void dropout_attention_cols_kernel(co
     }
 }
 
-dim3 grid_of(const WideSide& s, const WideTable& t) { return dim3(std::min<uint32_t>(t.first[kWideClasses], (s.compute_units ? s.compute_units : 1u) * kWideBlocksPerCu)); }
-
-// d a power of two from 4, heads * d at most kWideMaxD: what place_of relies on
-bool shape_ok(uint32_t heads, uint32_t d) { return d >= 4u && (d & (d - 1u)) == 0u && heads >= 1u && uint64_t(heads) * d <= kWideMaxD; }
-
 }  // namespace
 
 hipError_t launch_dropout_forward(const WideSide& s, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, const float* bias, uint64_t ldb,
@@ -582,7 +431,7 @@ hipError_t launch_dropout_forward(const WideSide& s, const float* q, uint64_t ld
     if (!shape_ok(heads, d) || (bias && ldb < heads)) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, heads * d);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;      // a side has at least one row, and an empty row is of class 1
-    hipLaunchKernelGGL(dropout_attention_forward_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, bias, ldb, heads, d, wide_group_lanes(heads * d), scale, dr,
+    hipLaunchKernelGGL(dropout_attention_forward_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, bias, ldb, heads, d, wide_group_lanes(heads * d), scale, dr,
                        y, ldy, lse, ldl);
     return hipGetLastError();
 }
@@ -593,7 +442,7 @@ hipError_t launch_dropout_rows(const WideSide& s, const float* q, uint64_t ldq, 
     if (!shape_ok(heads, d) || ldd < heads || (bias && ldb < heads)) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, heads * d);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dropout_attention_rows_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, bias, ldb, heads, d,
+    hipLaunchKernelGGL(dropout_attention_rows_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, bias, ldb, heads, d,
                        wide_group_lanes(heads * d), scale, dr, gq, ldgq, dsum, ldd);
     return hipGetLastError();
 }
@@ -604,7 +453,7 @@ hipError_t launch_dropout_cols(const WideSide& s, const float* q, uint64_t ldq, 
     if (!shape_ok(heads, d) || ldd < heads || (bias && ldb < heads) || (gbias && ldgb < heads) || !s.perm) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, heads * d);
     if (t.first[kWideClasses] == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dropout_attention_cols_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.perm, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, dsum, ldd, bias, ldb, heads, d,
+    hipLaunchKernelGGL(dropout_attention_cols_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.perm, s.list, t, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, dsum, ldd, bias, ldb, heads, d,
                        wide_group_lanes(heads * d), scale, dr, gk, ldgk, gv, ldgv, gbias, ldgb);
     return hipGetLastError();
 }

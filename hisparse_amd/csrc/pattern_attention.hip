@@ -12,6 +12,10 @@
 //   fetch it by a shuffle: one exp per lane and trip, not four, and the same words;
 //   the groups of a team merge by lane shuffles -- the maximum first, then each group's rescaled sums are added -- and a long row's four
 //   wavefronts through LDS (the 8 KiB of doubles of the gather kernel, plus m and l per wavefront).
+// This file owns attend_entries, the stores of a last chunk of fewer than four words (a row of any d <= 256), the kernel and its launcher.
+// The State with its raise_to and merge_states, and class_of, are wide_lanes.h's.  The kernel writes that header's pick and trips_of out
+// in its own body, one of the two copies left beside the header (wide_dot_kernel has the other): with the calls it compiles to other
+// code, and the header was made without moving any kernel's code.
 // Every output word has one writer: no atomics, no scratch, no matrix engine, no inline assembly.  Arithmetic: the header's ARITHMETIC
 // block -- fp32 products of Q and K added in double and rounded once, one fp32 multiply by scale, everything after that in double with
 // the library's exp and log, one rounding per output word.
@@ -21,55 +25,13 @@
 #include <cstdint>
 
 #include "pattern_attention.h"
+#include "wide_lanes.h"
 
 namespace hisparse {
 namespace dev {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr uint32_t kWaves = kWideThreads / 64;
-
-struct Sum4 {
-    double a, b, c, d;
-};
-
-// the online softmax state of one group for its chunk of the row
-struct State {
-    float m;      // one of the t words, or -inf
-    double l;
-    Sum4 acc;
-};
-
-__device__ __forceinline__ void scale_state(State& s, double f) {
-    s.l *= f;
-    s.acc.a *= f;
-    s.acc.b *= f;
-    s.acc.c *= f;
-    s.acc.d *= f;
-}
-
-// NaN is never the maximum (fmaxf returns the other operand)
-__device__ __forceinline__ void raise_to(State& s, float m_new) {
-    if (m_new != s.m) {      // m_new > s.m: exp(-inf - finite) = 0 for a state that is still empty
-        scale_state(s, exp(static_cast<double>(s.m) - static_cast<double>(m_new)));
-        s.m = m_new;
-    }
-}
-
-// the states of the lanes that differ in the bits from..to/2 of the lane index become one: the maximum first, then the rescaled sums
-__device__ __forceinline__ void merge_lanes(State& s, uint32_t from, uint32_t to) {
-    float m = s.m;
-    for (uint32_t k = from; k < to; k <<= 1) m = fmaxf(m, __shfl_xor(m, int(k), 64));
-    raise_to(s, m);
-    for (uint32_t k = from; k < to; k <<= 1) {
-        s.l += __shfl_xor(s.l, int(k), 64);
-        s.acc.a += __shfl_xor(s.acc.a, int(k), 64);
-        s.acc.b += __shfl_xor(s.acc.b, int(k), 64);
-        s.acc.c += __shfl_xor(s.acc.c, int(k), 64);
-        s.acc.d += __shfl_xor(s.acc.d, int(k), 64);
-    }
-}
+using namespace lanes;      // State is one group's here: every lane of a group holds the same m and l
 
 // the first `words` (1 ... 4) of a chunk of Y = acc / l
 __device__ __forceinline__ void store_chunk(float* dst, const Sum4& s, double l, uint32_t words) {
@@ -93,13 +55,6 @@ __device__ __forceinline__ void store_zeros(float* dst, uint32_t words) {
         if (words >= 2u) dst[1] = 0.0f;
         if (words >= 3u) dst[2] = 0.0f;
     }
-}
-
-__device__ __forceinline__ uint32_t class_of(const WideTable& t, uint64_t w) {
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < kWideClasses; ++k) c += w >= t.first[k] ? 1u : 0u;
-    return c;
 }
 
 // One row's entries lo + g, lo + g + groups, ... through this group's state.  Every lane of the wavefront makes `trips` trips (the most
@@ -169,7 +124,6 @@ __device__ __forceinline__ void attend_entries(State& st, const uint32_t* __rest
         }
     }
 }
-static_assert(kWideInFlight == 4, "a trip's weights are dealt to four lanes of a group");
 
 __global__ __launch_bounds__(kWideThreads) void pattern_attention_kernel(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ list,
                                                                         WideTable tab, const float* __restrict__ q, uint64_t ldq, const float* __restrict__ k, uint64_t ldk,
@@ -184,6 +138,7 @@ __global__ __launch_bounds__(kWideThreads) void pattern_attention_kernel(const u
     const uint32_t words = live ? min(d - at, 4u) : 0u;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint64_t w = blockIdx.x; w < tab.first[kWideClasses]; w += gridDim.x) {
+        // pick and trips_of of wide_lanes.h written out: with the calls this kernel compiles to other code (tools/device_asm_digest.py)
         const uint32_t c = class_of(tab, w);
         uint32_t r = 0, lo = 0, hi = 0, g, groups, team = 64u;
         bool mine = true;
@@ -212,7 +167,7 @@ __global__ __launch_bounds__(kWideThreads) void pattern_attention_kernel(const u
         const f32x4 qv = *reinterpret_cast<const f32x4*>(q + uint64_t(r) * ldq + at);      // held for the whole row
         State st = {-INFINITY, 0.0, {0.0, 0.0, 0.0, 0.0}};
         attend_entries(st, idx, qv, words, k + at, ldk, v + at, ldv, scale, lo, hi, g, groups, group, trips);
-        merge_lanes(st, group, team);
+        merge_states(st, group, team);
         float* dst = y + uint64_t(r) * ldy + at;
         if (c != 0) {
             if (mine && g == 0 && live) {
@@ -251,8 +206,6 @@ __global__ __launch_bounds__(kWideThreads) void pattern_attention_kernel(const u
     }
 }
 
-static_assert(kWaves == 4, "the long rows' merge reads four states");
-
 }  // namespace
 
 hipError_t launch_pattern_attention(const WideSide& s, const float* q, uint64_t ldq, const float* k, uint64_t ldk, const float* v, uint64_t ldv, uint32_t d, float scale, float* y,
@@ -260,8 +213,7 @@ hipError_t launch_pattern_attention(const WideSide& s, const float* q, uint64_t 
     if (d == 0 || d > kWideMaxD) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, d);
     if (t.first[kWideClasses] == 0) return hipSuccess;
-    const dim3 grid(std::min<uint32_t>(t.first[kWideClasses], (s.compute_units ? s.compute_units : 1u) * kWideBlocksPerCu));
-    hipLaunchKernelGGL(pattern_attention_kernel, grid, dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, d, wide_group_lanes(d), scale, y, ldy, lse);
+    hipLaunchKernelGGL(pattern_attention_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, q, ldq, k, ldk, v, ldv, d, wide_group_lanes(d), scale, y, ldy, lse);
     return hipGetLastError();
 }
 

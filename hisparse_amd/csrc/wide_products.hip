@@ -14,24 +14,21 @@
 // wavefronts' through 8 KiB of LDS; the dot kernel holds U's chunk in registers for the whole row, adds the lanes of a group by shuffles
 // per entry and needs no LDS.  Every output word has one writer: no atomics, no scratch, no matrix engine, no inline assembly.
 // Arithmetic: the header's ARITHMETIC block -- one fp32 multiply per product (-ffp-contract=off), added in double, rounded once.
+// class_of, Sum4 and grid_of are wide_lanes.h's, the device side of this schedule that the attention kernels share.  These two kernels
+// keep their own reading of a team's row (team_row: no trip count on the gather side), older than that header's pick.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 
+#include "wide_lanes.h"
 #include "wide_products.h"
 
 namespace hisparse {
 namespace dev {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr uint32_t kWaves = kWideThreads / 64;
-
-struct Sum4 {
-    double a, b, c, d;
-};
+using namespace lanes;
 
 __device__ __forceinline__ void add_row(Sum4& s, float w, f32x4 x) {
     s.a += static_cast<double>(w * x.x);
@@ -58,14 +55,6 @@ __device__ __forceinline__ void store_chunk(float* dst, const Sum4& s, uint32_t 
         if (words >= 2u) dst[1] = b;
         if (words >= 3u) dst[2] = c;
     }
-}
-
-// the class that holds virtual workgroup w: first[] never decreases, and an empty class shares its first workgroup with the next one
-__device__ __forceinline__ uint32_t class_of(const WideTable& t, uint64_t w) {
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < kWideClasses; ++k) c += w >= t.first[k] ? 1u : 0u;
-    return c;
 }
 
 // The row of this lane's team in virtual workgroup w of class c: r, its entries [lo, hi) and whether there is one (a team past the end of
@@ -151,7 +140,6 @@ __global__ __launch_bounds__(kWideThreads) void wide_gather_kernel(const uint32_
         }
     }
 }
-static_assert(kWaves == 4, "the long rows' sums read four words");
 
 // One row of the dot kernel: every lane of the wavefront makes `trips` trips (the most any of its teams needs: the shuffles below stay
 // convergent), a group takes entries lo + g, + groups, ...; the lanes of a group add their chunks' sums and the first one stores.
@@ -197,6 +185,7 @@ __global__ __launch_bounds__(kWideThreads) void wide_dot_kernel(const uint32_t* 
     const uint32_t at = live ? chunk * 4u : 0u;
     const uint32_t words = live ? min(d - at, 4u) : 0u;
     for (uint64_t w = blockIdx.x; w < t.first[kWideClasses]; w += gridDim.x) {
+        // pick and trips_of of wide_lanes.h written out (team_row): with the calls this kernel compiles to other code (tools/device_asm_digest.py)
         const uint32_t c = class_of(t, w);
         uint32_t r, lo, hi, g, groups;
         if (c != 0) {
@@ -220,17 +209,13 @@ __global__ __launch_bounds__(kWideThreads) void wide_dot_kernel(const uint32_t* 
     }
 }
 
-dim3 grid_of(const WideSide& s, const WideTable& t) {
-    return dim3(std::min<uint32_t>(t.first[kWideClasses], (s.compute_units ? s.compute_units : 1u) * kWideBlocksPerCu));
-}
-
 }  // namespace
 
 hipError_t launch_wide_dot(const WideSide& s, const float* u, uint64_t ldu, const float* v, uint64_t ldv, uint32_t d, float* out, hipStream_t stream) {
     if (d == 0 || d > kWideMaxD) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, d);
     if (s.entries == 0) return hipSuccess;      // nothing to write
-    hipLaunchKernelGGL(wide_dot_kernel, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, u, ldu, v, ldv, d, wide_group_lanes(d), out);
+    hipLaunchKernelGGL(wide_dot_kernel, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.list, t, u, ldu, v, ldv, d, wide_group_lanes(d), out);
     return hipGetLastError();
 }
 
@@ -238,8 +223,8 @@ hipError_t launch_wide_gather(const WideSide& s, const float* w, const float* x,
     if (d == 0 || d > kWideMaxD) return hipErrorInvalidValue;
     const WideTable t = wide_table(s.count, d);
     if (t.first[kWideClasses] == 0) return hipSuccess;
-    if (s.perm) hipLaunchKernelGGL(wide_gather_kernel<true>, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.perm, s.list, t, w, x, ldx, d, wide_group_lanes(d), y, ldy);
-    else hipLaunchKernelGGL(wide_gather_kernel<false>, grid_of(s, t), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.perm, s.list, t, w, x, ldx, d, wide_group_lanes(d), y, ldy);
+    if (s.perm) hipLaunchKernelGGL(wide_gather_kernel<true>, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.perm, s.list, t, w, x, ldx, d, wide_group_lanes(d), y, ldy);
+    else hipLaunchKernelGGL(wide_gather_kernel<false>, grid_of(s, t, kWideBlocksPerCu), dim3(kWideThreads), 0, stream, s.ptr, s.idx, s.perm, s.list, t, w, x, ldx, d, wide_group_lanes(d), y, ldy);
     return hipGetLastError();
 }
 
