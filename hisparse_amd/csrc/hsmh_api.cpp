@@ -13,6 +13,9 @@
 // (heads_dropout_attention.hip): no new object and no memory; the backward keys its column side's draws through the same map.
 // The four hsgat_* calls of include/hisparse_gat.h run the graph attention (GAT) step on the same object (gat_attention.hip): additive
 // scores from one word per node and head, the same pattern, transposed pattern, D words and stream, no map and no memory of their own.
+// The six hsgat2_* calls of include/hisparse_gatv2.h run the GATv2 step on the same object (gatv2_attention.hip): the score is
+// a . LeakyReLU(XD[row] + XS[col]); the backward's third launch adds the row side's per-workgroup vectors of ga, which live in a
+// workspace the CALLER owns (hsgat2_work_bytes), so the object still allocates nothing outside create.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -21,11 +24,13 @@
 
 #include "device_buffer.h"
 #include "gat_attention.h"
+#include "gatv2_attention.h"
 #include "heads16_attention.h"
 #include "heads_attention.h"
 #include "heads_bias_attention.h"
 #include "heads_dropout_attention.h"
 #include "hisparse_gat.h"
+#include "hisparse_gatv2.h"
 #include "hisparse_heads_bf16.h"
 #include "hisparse_heads_bias.h"
 #include "hisparse_heads_dropout.h"
@@ -645,6 +650,106 @@ int hsgat_backward(hsmh_pattern* p, const float* el, const float* er, const floa
         hipError_t e = hipMemcpyAsync(gel, d_gel.get(), size_t(p->num_rows) * heads * 4, hipMemcpyDeviceToHost, p->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(ger, d_ger.get(), size_t(p->num_cols) * heads * 4, hipMemcpyDeviceToHost, p->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(gv, d_gv.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+// ---- include/hisparse_gatv2.h: the same object, the score a . LeakyReLU(XD[row] + XS[col]) and the gradient of a ---------------------------
+int hsgat2_forward_device(hsmh_pattern* p, const float* xd_dev, uint64_t ldxd, const float* xs_dev, uint64_t ldxs, const float* a_dev, uint32_t heads, uint32_t d, float slope,
+                          float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat2_forward(p->num_rows, p->num_cols, p->max_heads, xd_dev, ldxd, xs_dev, ldxs, a_dev, heads, d, slope, y_dev, ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HSMH_HIP(p, launch_gatv2_forward(p->rows, xd_dev, ldxd, xs_dev, ldxs, a_dev, heads, d, slope, y_dev, ldy, lse_dev, ldl, p->stream));
+    return HS_OK;
+}
+
+int hsgat2_forward(hsmh_pattern* p, const float* xd, const float* xs, const float* a, uint32_t heads, uint32_t d, float slope, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat2_forward_host(p->num_rows, p->num_cols, p->max_heads, xd, xs, a, heads, d, slope, y, lse, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    DeviceBuffer<float> d_xd, d_xs, d_a, d_y, d_lse;      // transient (the host form is synchronous and may allocate)
+    if (int rc = features_in(p, d_xd, xd, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_xs, xs, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_a, a, 1, w)) return rc;
+    HSMH_HIP(p, d_y.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_lse.alloc_count(size_t(p->num_rows) * heads, 16));
+    int rc = hsgat2_forward_device(p, d_xd.get(), w, d_xs.get(), w, d_a.get(), heads, d, slope, d_y.get(), w, lse ? d_lse.get() : nullptr, heads);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(y, d_y.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess && lse) e = hipMemcpyAsync(lse, d_lse.get(), size_t(p->num_rows) * heads * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
+    }
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
+    return rc;
+}
+
+// one vector of heads * d doubles per physical workgroup of the row side's launch
+int hsgat2_work_bytes(const hsmh_pattern* p, uint32_t heads, uint32_t d, uint64_t* bytes) {
+    if (!p || !bytes) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (hisparse::hsmh::check_shape(heads, d, p->max_heads, why)) return HS_ERR_BAD_ARG;      // p is const: the reason is check_shape's, as the calls report it
+    *bytes = uint64_t(gatv2_row_vectors(p->rows, heads, d)) * heads * d * 8;
+    return HS_OK;
+}
+
+int hsgat2_backward_device(hsmh_pattern* p, const float* xd_dev, uint64_t ldxd, const float* xs_dev, uint64_t ldxs, const float* a_dev, const float* gy_dev, uint64_t ldgy,
+                           const float* lse_dev, uint64_t ldl, uint32_t heads, uint32_t d, float slope, float* gxd_dev, uint64_t ldgxd, float* gxs_dev, uint64_t ldgxs, float* ga_dev,
+                           void* work_dev, uint64_t work_bytes) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    uint64_t need = 0;
+    (void)hsgat2_work_bytes(p, heads, d, &need);      // a bad shape leaves 0 and is refused by the checks below, with its reason
+    if (int rc = hisparse::hsmh::check_gat2_backward(p->num_rows, p->num_cols, p->max_heads, p->backward, xd_dev, ldxd, xs_dev, ldxs, a_dev, gy_dev, ldgy, lse_dev, ldl, heads, d, slope,
+                                                     gxd_dev, ldgxd, gxs_dev, ldgxs, ga_dev, work_dev, work_bytes, need, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    double* work = static_cast<double*>(work_dev);
+    HSMH_HIP(p, launch_gatv2_backward_rows(p->rows, xd_dev, ldxd, xs_dev, ldxs, a_dev, gy_dev, ldgy, lse_dev, ldl, heads, d, slope, gxd_dev, ldgxd, p->dsum.get(), p->max_heads, work,
+                                           p->stream));
+    HSMH_HIP(p, launch_gatv2_backward_cols(p->cols, xd_dev, ldxd, xs_dev, ldxs, a_dev, gy_dev, ldgy, lse_dev, ldl, p->dsum.get(), p->max_heads, heads, d, slope, gxs_dev, ldgxs,
+                                           p->stream));
+    HSMH_HIP(p, launch_gatv2_reduce(work, gatv2_row_vectors(p->rows, heads, d), heads * d, ga_dev, p->stream));
+    return HS_OK;
+}
+
+int hsgat2_backward(hsmh_pattern* p, const float* xd, const float* xs, const float* a, const float* gy, const float* lse, uint32_t heads, uint32_t d, float slope, float* gxd,
+                    float* gxs, float* ga) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat2_backward_host(p->num_rows, p->num_cols, p->max_heads, p->backward, xd, xs, a, gy, lse, heads, d, slope, gxd, gxs, ga, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    uint64_t work_bytes = 0;
+    if (hsgat2_work_bytes(p, heads, d, &work_bytes)) return fail(p, HS_ERR_BAD_ARG, "hsgat2_work_bytes refused a shape the checks accepted");
+    DeviceBuffer<float> d_xd, d_xs, d_a, d_gy, d_lse, d_gxd, d_gxs, d_ga;      // transient (the host form is synchronous and may allocate)
+    DeviceBuffer<double> d_work;
+    if (int rc = features_in(p, d_xd, xd, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_xs, xs, p->num_cols, w)) return rc;
+    if (int rc = features_in(p, d_a, a, 1, w)) return rc;
+    if (int rc = features_in(p, d_gy, gy, p->num_rows, w)) return rc;
+    if (int rc = features_in(p, d_lse, lse, p->num_rows, heads)) return rc;
+    HSMH_HIP(p, d_gxd.alloc_count(size_t(p->num_rows) * w, 16));
+    HSMH_HIP(p, d_gxs.alloc_count(size_t(p->num_cols) * w, 16));
+    HSMH_HIP(p, d_ga.alloc_count(w, 16));
+    HSMH_HIP(p, d_work.alloc_count(size_t(work_bytes / 8), 16));
+    int rc = hsgat2_backward_device(p, d_xd.get(), w, d_xs.get(), w, d_a.get(), d_gy.get(), w, d_lse.get(), heads, heads, d, slope, d_gxd.get(), w, d_gxs.get(), w, d_ga.get(),
+                                    d_work.get(), work_bytes);
+    // copy out when all went well, always wait before the transient buffers go
+    if (rc == HS_OK) {
+        hipError_t e = hipMemcpyAsync(gxd, d_gxd.get(), size_t(p->num_rows) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(gxs, d_gxs.get(), size_t(p->num_cols) * w * 4, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ga, d_ga.get(), size_t(w) * 4, hipMemcpyDeviceToHost, p->stream);
         if (e != hipSuccess) rc = hip_fail(p, e, "copying the result out");
     }
     const hipError_t e = hipStreamSynchronize(p->stream);

@@ -4,7 +4,8 @@
 // the width heads * d.  The calls with a bias of include/hisparse_heads_bias.h add the checks of their two per-entry arrays, and the
 // calls with dropout of include/hisparse_heads_dropout.h those of drop_p and of a bias that may be null, at the end, with hsmhd_keep_mask
 // itself, which both libraries export; the calls of include/hisparse_gat.h (additive scores from one word per node and head) their
-// slope and the checks of the five head arrays, after that.  Host code only.
+// slope and the checks of the five head arrays, after that; the calls of include/hisparse_gatv2.h the checks of a, ga and the caller's
+// workspace, last.  Host code only.
 #ifndef HISPARSE_HSMH_COMMON_H_
 #define HISPARSE_HSMH_COMMON_H_
 
@@ -509,6 +510,117 @@ inline int check_gat_backward_host(uint32_t num_rows, uint32_t num_cols, uint32_
     const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4, rh = uint64_t(num_rows) * heads * 4, ch = uint64_t(num_cols) * heads * 4;
     const hsab::Range in[5] = {{"el", el, rh}, {"er", er, ch}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, rh}};
     const hsab::Range out[3] = {{"gel", gel, rh}, {"ger", ger, ch}, {"gv", gv, cb}};
+    return hsab::check_overlaps(in, out, why);
+}
+
+// ---- the calls of include/hisparse_gatv2.h: the score a[h] . LeakyReLU(XD[row] + XS[col]); a and ga are heads * d contiguous words ------
+
+// a or ga: heads * d contiguous fp32 words, 16-byte aligned, no ld
+inline int check_head_vector(const char* name, const float* p, std::string& why) {
+    if (!p) {
+        why = std::string("null ") + name;
+        return HS_ERR_BAD_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(p) % 16) {
+        why = std::string(name) + " must be 16-byte aligned";
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+// the workspace of hsgat2_backward_device: at least `need` bytes (what hsgat2_work_bytes says), 16-byte aligned
+inline int check_work(const void* work, uint64_t work_bytes, uint64_t need, std::string& why) {
+    if (!work) {
+        why = "null workspace";
+        return HS_ERR_BAD_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(work) % 16) {
+        why = "the workspace must be 16-byte aligned";
+        return HS_ERR_BAD_ARG;
+    }
+    if (work_bytes < need) {
+        why = "the workspace is smaller than hsgat2_work_bytes says for this object, heads and d";
+        return HS_ERR_BAD_ARG;
+    }
+    return HS_OK;
+}
+
+// hsgat2_forward_device's arguments
+inline int check_gat2_forward(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, const float* xd, uint64_t ldxd, const float* xs, uint64_t ldxs, const float* a, uint32_t heads,
+                              uint32_t d, float slope, const float* y, uint64_t ldy, const float* lse, uint64_t ldl, std::string& why) {
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    const uint32_t w = heads * d;
+    if (int rc = hsw::check_features("xd", xd, ldxd, w, why)) return rc;
+    if (int rc = hsw::check_features("xs", xs, ldxs, w, why)) return rc;
+    if (int rc = check_head_vector("a", a, why)) return rc;
+    if (int rc = hsw::check_features("y", y, ldy, w, why)) return rc;
+    if (lse)
+        if (int rc = check_lse(lse, ldl, heads, why)) return rc;
+    if (int rc = check_slope(slope, why)) return rc;
+    return hsat::check_overlaps(xd, hsat::reach(num_rows, ldxd, w), xs, hsat::reach(num_cols, ldxs, w), a, uint64_t(w) * 4, y, hsat::reach(num_rows, ldy, w), lse,
+                                lse_reach(num_rows, ldl, heads), why);
+}
+
+// hsgat2_forward's: ld = heads * d, ldl = heads, no alignment rule
+inline int check_gat2_forward_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, const float* xd, const float* xs, const float* a, uint32_t heads, uint32_t d, float slope,
+                                   const float* y, const float* lse, std::string& why) {
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    if (!xd || !xs || !a || !y) {
+        why = "null argument";
+        return HS_ERR_BAD_ARG;
+    }
+    if (int rc = check_slope(slope, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4;
+    return hsat::check_overlaps(xd, rb, xs, cb, a, uint64_t(heads) * d * 4, y, rb, lse, uint64_t(num_rows) * heads * 4, why);
+}
+
+// what the two backward forms share: the three outputs against the five inputs and each other, and the workspace (null in the host
+// form) against all eight
+inline int check_gat2_overlaps(const hsab::Range (&in)[5], const hsab::Range (&out)[3], const void* work, uint64_t work_bytes, std::string& why) {
+    if (int rc = hsab::check_overlaps(in, out, why)) return rc;
+    for (const hsab::Range& i : in)
+        if (int rc = check_apart("the workspace", work, work_bytes, i.name, i.p, i.bytes, why)) return rc;
+    for (const hsab::Range& o : out)
+        if (int rc = check_apart("the workspace", work, work_bytes, o.name, o.p, o.bytes, why)) return rc;
+    return HS_OK;
+}
+
+// hsgat2_backward_device's arguments; `need` is what hsgat2_work_bytes says
+inline int check_gat2_backward(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool backward, const float* xd, uint64_t ldxd, const float* xs, uint64_t ldxs, const float* a,
+                               const float* gy, uint64_t ldgy, const float* lse, uint64_t ldl, uint32_t heads, uint32_t d, float slope, const float* gxd, uint64_t ldgxd, const float* gxs,
+                               uint64_t ldgxs, const float* ga, const void* work, uint64_t work_bytes, uint64_t need, std::string& why) {
+    if (int rc = check_backward_flag(backward, why)) return rc;
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    const uint32_t w = heads * d;
+    if (int rc = hsw::check_features("xd", xd, ldxd, w, why)) return rc;
+    if (int rc = hsw::check_features("xs", xs, ldxs, w, why)) return rc;
+    if (int rc = check_head_vector("a", a, why)) return rc;
+    if (int rc = hsw::check_features("gy", gy, ldgy, w, why)) return rc;
+    if (int rc = check_lse(lse, ldl, heads, why)) return rc;
+    if (int rc = hsw::check_features("gxd", gxd, ldgxd, w, why)) return rc;
+    if (int rc = hsw::check_features("gxs", gxs, ldgxs, w, why)) return rc;
+    if (int rc = check_head_vector("ga", ga, why)) return rc;
+    if (int rc = check_slope(slope, why)) return rc;
+    if (int rc = check_work(work, work_bytes, need, why)) return rc;
+    const hsab::Range in[5] = {{"xd", xd, hsat::reach(num_rows, ldxd, w)}, {"xs", xs, hsat::reach(num_cols, ldxs, w)}, {"a", a, uint64_t(w) * 4}, {"gy", gy, hsat::reach(num_rows, ldgy, w)},
+                               {"lse", lse, lse_reach(num_rows, ldl, heads)}};
+    const hsab::Range out[3] = {{"gxd", gxd, hsat::reach(num_rows, ldgxd, w)}, {"gxs", gxs, hsat::reach(num_cols, ldgxs, w)}, {"ga", ga, uint64_t(w) * 4}};
+    return check_gat2_overlaps(in, out, work, work_bytes, why);
+}
+
+// hsgat2_backward's: ld = heads * d, ldl = heads, no alignment rule, no workspace
+inline int check_gat2_backward_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool backward, const float* xd, const float* xs, const float* a, const float* gy,
+                                    const float* lse, uint32_t heads, uint32_t d, float slope, const float* gxd, const float* gxs, const float* ga, std::string& why) {
+    if (int rc = check_backward_flag(backward, why)) return rc;
+    if (int rc = check_shape(heads, d, max_heads, why)) return rc;
+    if (!xd || !xs || !a || !gy || !lse || !gxd || !gxs || !ga) {
+        why = "null argument";
+        return HS_ERR_BAD_ARG;
+    }
+    if (int rc = check_slope(slope, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4, ab = uint64_t(heads) * d * 4;
+    const hsab::Range in[5] = {{"xd", xd, rb}, {"xs", xs, cb}, {"a", a, ab}, {"gy", gy, rb}, {"lse", lse, uint64_t(num_rows) * heads * 4}};
+    const hsab::Range out[3] = {{"gxd", gxd, rb}, {"gxs", gxs, cb}, {"ga", ga, ab}};
     return hsab::check_overlaps(in, out, why);
 }
 

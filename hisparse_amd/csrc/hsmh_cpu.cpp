@@ -18,6 +18,9 @@
 // With drop_p = 0 every w is 1.0 and the loops form the words of the calls without dropout.
 // The four hsgat_* calls of include/hisparse_gat.h run loops of their own (gat_forward_head, gat_backward_head): the score is
 // x = el[row] + er[col], one fp32 add, and t = x > 0 ? x : slope * x, one fp32 multiply; the rest in double as above; gel = A - D B.
+// The six hsgat2_* calls of include/hisparse_gatv2.h run loops of their own too (gat2_forward_head, gat2_backward_head): z = xd + xs and
+// w = LeakyReLU(z) per word, t = a . w with fp32 products added in double; gXD = a (A - D B) per word, and ga is the rows' A' - D B' added
+// in row order in the doubles of the caller's workspace (ONE vector here) and rounded once.
 // No dependency beyond the headers and hsmh_common.h: tests/cpp/test_heads_cpu.cpp compiles this file alone under the sanitizers.
 #include <cmath>
 #include <cstring>
@@ -27,6 +30,7 @@
 #include <vector>
 
 #include "hisparse_gat.h"
+#include "hisparse_gatv2.h"
 #include "hisparse_heads_bf16.h"
 #include "hisparse_heads_bias.h"
 #include "hisparse_heads_dropout.h"
@@ -286,6 +290,126 @@ void gat_backward(const hsmh_pattern* p, const float* el, uint64_t ldel, const f
                   uint64_t ldl, uint32_t heads, uint32_t d, float slope, float* gel, uint64_t ldgel, float* ger, uint64_t ldger, float* gv, uint64_t ldgv) {
     for (uint32_t h = 0; h < heads; ++h)
         gat_backward_head(p, el + h, ldel, er + h, lder, v + h * d, ldv, gy + h * d, ldgy, lse + h, ldl, d, slope, gel + h, ldgel, ger + h, ldger, gv + h * d, ldgv);
+}
+
+// ---- include/hisparse_gatv2.h: one head; xd, xs, a, gy, y, gxd, gxs and ga point at the head's first word, lse at its word of row 0 --------
+// t = fl32(sum_j fl32(a_j * w_j)), w_j = LeakyReLU(fl32(xd_j + xs_j)): fp32 products added in double, one rounding
+inline float gat2_score(const float* xd, const float* xs, const float* a, uint32_t d, float slope) {
+    double s = 0.0;
+    for (uint32_t j = 0; j < d; ++j) s += double(a[j] * gat_leaky(gat_score(xd[j], xs[j]), slope));
+    return float(s);
+}
+
+void gat2_forward_head(const hsmh_pattern* p, const float* xd, uint64_t ldxd, const float* xs, uint64_t ldxs, const float* a, uint32_t d, float slope, float* y, uint64_t ldy, float* lse,
+                       uint64_t ldl) {
+    const float ninf = -std::numeric_limits<float>::infinity();
+    std::vector<float> t;
+    std::vector<double> acc(d);
+    for (uint32_t r = 0; r < p->num_rows; ++r) {
+        const uint64_t lo = p->indptr[r], hi = p->indptr[r + 1];
+        float* dst = y + uint64_t(r) * ldy;
+        if (lo == hi) {
+            for (uint32_t j = 0; j < d; ++j) dst[j] = 0.0f;
+            if (lse) lse[uint64_t(r) * ldl] = ninf;
+            continue;
+        }
+        const float* x = xd + uint64_t(r) * ldxd;
+        t.resize(hi - lo);
+        float m = ninf;      // one of the t words; a NaN is never the maximum
+        for (uint64_t e = lo; e < hi; ++e) {
+            t[e - lo] = gat2_score(x, xs + uint64_t(p->indices[e]) * ldxs, a, d, slope);
+            m = std::fmax(m, t[e - lo]);
+        }
+        double l = 0.0;
+        acc.assign(d, 0.0);
+        for (uint64_t e = lo; e < hi; ++e) {
+            // a -inf score weighs exactly 0, also while the maximum is -inf itself; a NaN, or +inf under a maximum of +inf, gives NaN
+            const double w = t[e - lo] == ninf ? 0.0 : std::exp(double(t[e - lo]) - double(m));
+            const float* b = xs + uint64_t(p->indices[e]) * ldxs;
+            l += w;
+            for (uint32_t j = 0; j < d; ++j) acc[j] += w * double(b[j]);
+        }
+        for (uint32_t j = 0; j < d; ++j) dst[j] = float(acc[j] / l);
+        if (lse) lse[uint64_t(r) * ldl] = float(double(m) + std::log(l));
+    }
+}
+
+// ga_sum: d doubles, the head's words of the caller's workspace (or of the host form's own), rounded once into ga at the end
+void gat2_backward_head(const hsmh_pattern* p, const float* xd, uint64_t ldxd, const float* xs, uint64_t ldxs, const float* a, const float* gy, uint64_t ldgy, const float* lse,
+                        uint64_t ldl, uint32_t d, float slope, float* gxd, uint64_t ldgxd, float* gxs, uint64_t ldgxs, float* ga, double* ga_sum) {
+    std::vector<double> w, gp, sa(d), sb(d), ta(d), tb(d);
+    std::vector<double> sum_v(size_t(p->num_cols) * d, 0.0), sum_z(size_t(p->num_cols) * d, 0.0);
+    std::vector<uint32_t> count(p->num_cols, 0);
+    for (uint32_t j = 0; j < d; ++j) ga_sum[j] = 0.0;
+    for (uint32_t r = 0; r < p->num_rows; ++r) {
+        const uint64_t lo = p->indptr[r], hi = p->indptr[r + 1];
+        float* dst = gxd + uint64_t(r) * ldgxd;
+        if (lo == hi) {
+            for (uint32_t j = 0; j < d; ++j) dst[j] = 0.0f;
+            continue;
+        }
+        const float* x = xd + uint64_t(r) * ldxd;
+        const float* g = gy + uint64_t(r) * ldgy;
+        // a word that is not finite (a dead or bad row of the forward) makes every weight of the row's head NaN
+        const float lw = lse[uint64_t(r) * ldl];
+        const double l = std::isfinite(lw) ? double(lw) : std::numeric_limits<double>::quiet_NaN();
+        w.resize(hi - lo);
+        gp.resize(hi - lo);
+        double dsum = 0.0;      // D = sum P GP; per word A = sum P GP dz, B = sum P dz, A' = sum P GP w, B' = sum P w
+        sa.assign(d, 0.0);
+        sb.assign(d, 0.0);
+        ta.assign(d, 0.0);
+        tb.assign(d, 0.0);
+        for (uint64_t e = lo; e < hi; ++e) {
+            const float* c = xs + uint64_t(p->indices[e]) * ldxs;
+            double s = 0.0;
+            for (uint32_t j = 0; j < d; ++j) s += double(g[j] * c[j]);
+            const double pe = std::exp(double(gat2_score(x, c, a, d, slope)) - l);      // a -inf score under a finite lse weighs exactly 0
+            const double pg = pe * s;
+            w[e - lo] = pe;
+            gp[e - lo] = s;
+            dsum += pg;
+            for (uint32_t j = 0; j < d; ++j) {
+                const float z = gat_score(x[j], c[j]);
+                const double dz = gat_slope_at(z, slope), wj = double(gat_leaky(z, slope));
+                sa[j] += pg * dz;
+                sb[j] += pe * dz;
+                ta[j] += pg * wj;
+                tb[j] += pe * wj;
+            }
+        }
+        for (uint32_t j = 0; j < d; ++j) {
+            dst[j] = float(double(a[j]) * (sa[j] - dsum * sb[j]));
+            ga_sum[j] += ta[j] - dsum * tb[j];
+        }
+        for (uint64_t e = lo; e < hi; ++e) {
+            const uint32_t c = p->indices[e];
+            const float* b = xs + uint64_t(c) * ldxs;
+            const double pe = w[e - lo], gt = pe * (gp[e - lo] - dsum);
+            double* to_v = sum_v.data() + size_t(c) * d;
+            double* to_z = sum_z.data() + size_t(c) * d;
+            ++count[c];
+            for (uint32_t j = 0; j < d; ++j) {
+                to_v[j] += pe * double(g[j]);
+                to_z[j] += gt * gat_slope_at(gat_score(x[j], b[j]), slope);
+            }
+        }
+    }
+    for (uint32_t c = 0; c < p->num_cols; ++c) {      // a column without entries: +0.0 whatever a holds
+        for (uint32_t j = 0; j < d; ++j) gxs[uint64_t(c) * ldgxs + j] = count[c] ? float(sum_v[size_t(c) * d + j] + double(a[j]) * sum_z[size_t(c) * d + j]) : 0.0f;
+    }
+    for (uint32_t j = 0; j < d; ++j) ga[j] = float(ga_sum[j]);
+}
+
+void gat2_forward(const hsmh_pattern* p, const float* xd, uint64_t ldxd, const float* xs, uint64_t ldxs, const float* a, uint32_t heads, uint32_t d, float slope, float* y, uint64_t ldy,
+                  float* lse, uint64_t ldl) {
+    for (uint32_t h = 0; h < heads; ++h) gat2_forward_head(p, xd + h * d, ldxd, xs + h * d, ldxs, a + h * d, d, slope, y + h * d, ldy, lse ? lse + h : nullptr, ldl);
+}
+
+void gat2_backward(const hsmh_pattern* p, const float* xd, uint64_t ldxd, const float* xs, uint64_t ldxs, const float* a, const float* gy, uint64_t ldgy, const float* lse, uint64_t ldl,
+                   uint32_t heads, uint32_t d, float slope, float* gxd, uint64_t ldgxd, float* gxs, uint64_t ldgxs, float* ga, double* work) {
+    for (uint32_t h = 0; h < heads; ++h)
+        gat2_backward_head(p, xd + h * d, ldxd, xs + h * d, ldxs, a + h * d, gy + h * d, ldgy, lse + h, ldl, d, slope, gxd + h * d, ldgxd, gxs + h * d, ldgxs, ga + h * d, work + h * d);
 }
 
 }  // namespace
@@ -557,6 +681,61 @@ int hsgat_backward(hsmh_pattern* p, const float* el, const float* er, const floa
         return fail(p, rc, why);
     const uint64_t w = uint64_t(heads) * d;
     gat_backward(p, el, heads, er, heads, v, w, gy, w, lse, heads, heads, d, slope, gel, heads, ger, heads, gv, w);
+    return HS_OK;
+}
+
+// ---- include/hisparse_gatv2.h: the same object, the score a . LeakyReLU(XD[row] + XS[col]) and the gradient of a ----------------------
+int hsgat2_forward_device(hsmh_pattern* p, const float* xd_dev, uint64_t ldxd, const float* xs_dev, uint64_t ldxs, const float* a_dev, uint32_t heads, uint32_t d, float slope,
+                          float* y_dev, uint64_t ldy, float* lse_dev, uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat2_forward(p->num_rows, p->num_cols, p->max_heads, xd_dev, ldxd, xs_dev, ldxs, a_dev, heads, d, slope, y_dev, ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    gat2_forward(p, xd_dev, ldxd, xs_dev, ldxs, a_dev, heads, d, slope, y_dev, ldy, lse_dev, ldl);
+    return HS_OK;
+}
+
+int hsgat2_forward(hsmh_pattern* p, const float* xd, const float* xs, const float* a, uint32_t heads, uint32_t d, float slope, float* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat2_forward_host(p->num_rows, p->num_cols, p->max_heads, xd, xs, a, heads, d, slope, y, lse, why)) return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    gat2_forward(p, xd, w, xs, w, a, heads, d, slope, y, w, lse, heads);
+    return HS_OK;
+}
+
+// the sums of ga, heads * d doubles: this library adds the rows in order on one thread, so it keeps ONE vector
+int hsgat2_work_bytes(const hsmh_pattern* p, uint32_t heads, uint32_t d, uint64_t* bytes) {
+    if (!p || !bytes) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (hisparse::hsmh::check_shape(heads, d, p->max_heads, why)) return HS_ERR_BAD_ARG;
+    *bytes = uint64_t(heads) * d * 8;
+    return HS_OK;
+}
+
+int hsgat2_backward_device(hsmh_pattern* p, const float* xd_dev, uint64_t ldxd, const float* xs_dev, uint64_t ldxs, const float* a_dev, const float* gy_dev, uint64_t ldgy,
+                           const float* lse_dev, uint64_t ldl, uint32_t heads, uint32_t d, float slope, float* gxd_dev, uint64_t ldgxd, float* gxs_dev, uint64_t ldgxs, float* ga_dev,
+                           void* work_dev, uint64_t work_bytes) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    uint64_t need = 0;
+    (void)hsgat2_work_bytes(p, heads, d, &need);      // a bad shape leaves 0 and is refused by the checks below, with its reason
+    if (int rc = hisparse::hsmh::check_gat2_backward(p->num_rows, p->num_cols, p->max_heads, p->backward, xd_dev, ldxd, xs_dev, ldxs, a_dev, gy_dev, ldgy, lse_dev, ldl, heads, d, slope,
+                                                     gxd_dev, ldgxd, gxs_dev, ldgxs, ga_dev, work_dev, work_bytes, need, why))
+        return fail(p, rc, why);
+    gat2_backward(p, xd_dev, ldxd, xs_dev, ldxs, a_dev, gy_dev, ldgy, lse_dev, ldl, heads, d, slope, gxd_dev, ldgxd, gxs_dev, ldgxs, ga_dev, static_cast<double*>(work_dev));
+    return HS_OK;
+}
+
+int hsgat2_backward(hsmh_pattern* p, const float* xd, const float* xs, const float* a, const float* gy, const float* lse, uint32_t heads, uint32_t d, float slope, float* gxd,
+                    float* gxs, float* ga) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_gat2_backward_host(p->num_rows, p->num_cols, p->max_heads, p->backward, xd, xs, a, gy, lse, heads, d, slope, gxd, gxs, ga, why))
+        return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    std::vector<double> work(w);      // the host form's own transient
+    gat2_backward(p, xd, w, xs, w, a, gy, w, lse, heads, heads, d, slope, gxd, w, gxs, w, ga, work.data());
     return HS_OK;
 }
 

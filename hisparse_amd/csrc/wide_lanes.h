@@ -1,6 +1,6 @@
 // wide_lanes.h — the device side of wide_products.h's schedule, defined ONCE for every kernel that runs on it: wide_products.hip,
 // pattern_attention.hip, attention_backward.hip, heads_attention.hip, heads16_attention.hip, heads_bias_attention.hip,
-// heads_dropout_attention.hip and gat_attention.hip.  Only .hip files include it.  wide_products.h owns the table, the side and the
+// heads_dropout_attention.hip, gat_attention.hip and gatv2_attention.hip.  Only .hip files include it.  wide_products.h owns the table, the side and the
 // constants; this header owns what a lane does with them:
 //   which virtual workgroup gets which row (class_of, Work, pick) and how many trips a wavefront makes so that its shuffles stay
 //     convergent (trips_of);
