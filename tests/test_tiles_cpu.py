@@ -496,6 +496,27 @@ def test_device_buffer(tmp_path):
     assert out.returncode == 0 and "DEVICE BUFFER OK" in out.stdout, out.stdout + out.stderr
 
 
+def test_staging(tmp_path):
+    """What the pattern objects share on the host (pattern_object.h): Staging, the owner of a host form's transient device buffers, and
+    the bodies of destroy / last_error / info / set_stream / sync -- tests/cpp/test_staging.cpp, over a fake HIP runtime that the program
+    defines itself (host memory, an ordered log of the calls, the n-th call of a kind made to fail), built with ASan and UBSan and run
+    as a program of its own.  Round trips on the linear and the 2D path, empty and optional operands, a refused _device call, the
+    in-place buffer, every allocation and copy failing in turn (each buffer freed once, never before the stream was waited for), a
+    failing wait, and one family's create-time error text left alone by another's."""
+    import subprocess
+    rocm = "/opt/rocm/include"
+    if not os.path.exists(f"{rocm}/hip/hip_runtime_api.h"):
+        pytest.skip("no HIP headers")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "staging"
+    # the sanitizers' runtimes are linked into the program: it then starts whatever else the process environment preloads
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-static-libasan", "-static-libubsan", "-D__HIP_PLATFORM_AMD__", f"-I{rocm}", f"-I{root}/include", f"-I{root}/hisparse_amd/csrc",
+                           f"{root}/tests/cpp/test_staging.cpp", "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "STAGING OK" in out.stdout, out.stdout + out.stderr
+
+
 @pytest.mark.parametrize("impl,ob", [(0, 8), (2, 64)])
 def test_blocks_go_to_xcds_by_column_slice(impl, ob, monkeypatch):
     """Column-sliced matrices whose x outgrows an XCD's L2 (forced here: HISPARSE_XCD_AFFINITY=1): logical workgroups
