@@ -11,6 +11,7 @@ Layout:
   heads16.py   ctypes face of include/hisparse_heads_bf16.h (the same object with bf16 operands)
   heads_bias.py ctypes face of include/hisparse_heads_bias.h (the same object with a per-entry, per-head additive bias and its gradient)
   heads_dropout.py ctypes face of include/hisparse_heads_dropout.h (the same object with dropout on the attention weights, no mask stored)
+  heads16_dropout.py ctypes face of include/hisparse_heads_dropout_bf16.h (that bias and dropout over bf16 operands)
   gat.py       ctypes face of include/hisparse_gat.h (the same object with GAT's additive scores, el[row] + er[col] through a LeakyReLU)
   gatv2.py     ctypes face of include/hisparse_gatv2.h (the same object with GATv2's score, a . LeakyReLU(XD[row] + XS[col]), and the gradient of a)
   datasets.py  the reference's benchmark matrices as seeded stand-ins
@@ -28,7 +29,8 @@ from . import heads  # noqa: F401
 from . import heads16  # noqa: F401
 from . import heads_bias  # noqa: F401
 from . import heads_dropout  # noqa: F401
+from . import heads16_dropout  # noqa: F401
 from . import gat  # noqa: F401
 from . import gatv2  # noqa: F401
 
-__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads", "heads16", "heads_bias", "heads_dropout", "gat", "gatv2"]
+__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads", "heads16", "heads_bias", "heads_dropout", "heads16_dropout", "gat", "gatv2"]

@@ -13,6 +13,7 @@
 // side of the backward finds an entry's bias words and stores its gbias words through it.  hsmh_create builds the map and drops it.
 // The five hsmhd_* calls of include/hisparse_heads_dropout.h add dropout on the attention weights, with or without a bias
 // (heads_dropout_attention.hip): no new object and no memory; the backward keys its column side's draws through the same map.
+// The four hsmhd16_* calls of include/hisparse_heads_dropout_bf16.h are those calls with bf16 operands (heads16_dropout_attention.hip).
 // The four hsgat_* calls of include/hisparse_gat.h run the graph attention (GAT) step on the same object (gat_attention.hip): additive
 // scores from one word per node and head, the same pattern, transposed pattern, D words and stream, no map and no memory of their own.
 // The six hsgat2_* calls of include/hisparse_gatv2.h run the GATv2 step on the same object (gatv2_attention.hip): the score is
@@ -25,6 +26,7 @@
 #include "gat_attention.h"
 #include "gatv2_attention.h"
 #include "heads16_attention.h"
+#include "heads16_dropout_attention.h"
 #include "heads_attention.h"
 #include "heads_bias_attention.h"
 #include "heads_dropout_attention.h"
@@ -33,6 +35,7 @@
 #include "hisparse_heads_bf16.h"
 #include "hisparse_heads_bias.h"
 #include "hisparse_heads_dropout.h"
+#include "hisparse_heads_dropout_bf16.h"
 #include "hsmh_common.h"
 #include "wide_schedule.h"
 
@@ -45,7 +48,7 @@ struct hsmh_pattern : PatternObject {
     bool map = false;                // hsmhb_create with HSMH_BACKWARD: cols.perm is kept
     WideSideBuffers rows, cols;      // the pattern and its rows by class; with HSMH_BACKWARD: the transposed pattern and its columns by class
                                      // and, with the map, the CSR index of every entry of the transposed pattern (read by the kernels of
-                                     // heads_bias_attention.hip and heads_dropout_attention.hip only)
+                                     // heads_bias_attention.hip, heads_dropout_attention.hip and heads16_dropout_attention.hip only)
     DeviceBuffer<double> dsum;       // with HSMH_BACKWARD: D per row and head, [row][max_heads]: one backward call in flight per object
 };
 
@@ -371,6 +374,80 @@ int hsmhd_backward(hsmh_pattern* p, const float* q, const float* k, const float*
 
 // host code: no object, no device
 int hsmhd_keep_mask(uint64_t nnz, uint32_t heads, float drop_p, uint64_t seed, uint64_t offset, uint8_t* keep) { return hisparse::hsmh::keep_mask(nnz, heads, drop_p, seed, offset, keep); }
+
+// ---- include/hisparse_heads_dropout_bf16.h: the same object, bf16 operands, dropout on the attention weights, a bias or none ---------------
+int hsmhd16_forward_device(hsmh_pattern* p, const uint16_t* q_dev, uint64_t ldq, const uint16_t* k_dev, uint64_t ldk, const uint16_t* v_dev, uint64_t ldv, const float* bias_dev,
+                           uint64_t ldb, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed, uint64_t offset, uint16_t* y_dev, uint64_t ldy, float* lse_dev,
+                           uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_dropout16(p->num_rows, p->num_cols, p->max_heads, p->nnz, q_dev, ldq, k_dev, ldk, v_dev, ldv, bias_dev, ldb, heads, d, scale, drop_p, y_dev,
+                                                         ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HS_HIP(p, launch_bf16_drop_forward(p->rows.view, q_dev, ldq, k_dev, ldk, v_dev, ldv, bias_dev, ldb, heads, d, scale, hisparse::philox::dropout_of(drop_p, seed, offset), y_dev, ldy,
+                                         lse_dev, ldl, p->stream));
+    return HS_OK;
+}
+
+int hsmhd16_forward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const uint16_t* v, const float* bias, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed,
+                    uint64_t offset, uint16_t* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_dropout16_host(p->num_rows, p->num_cols, p->max_heads, p->nnz, q, k, v, bias, heads, d, scale, drop_p, y, lse, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    Staging st(p);
+    const uint16_t* d_q = st.in(q, p->num_rows, w, w);
+    const uint16_t* d_k = st.in(k, p->num_cols, w, w);
+    const uint16_t* d_v = st.in(v, p->num_cols, w, w);
+    const float* d_b = st.in(bias, p->nnz, heads, heads);
+    uint16_t* d_y = st.out(y, p->num_rows, w, w);
+    float* d_lse = st.out(lse, p->num_rows, heads, heads);
+    return st.finish(st.failed() ? st.failed() : hsmhd16_forward_device(p, d_q, w, d_k, w, d_v, w, d_b, heads, heads, d, scale, drop_p, seed, offset, d_y, w, d_lse,
+                                                                       heads));
+}
+
+int hsmhd16_backward_device(hsmh_pattern* p, const uint16_t* q_dev, uint64_t ldq, const uint16_t* k_dev, uint64_t ldk, const uint16_t* v_dev, uint64_t ldv, const uint16_t* gy_dev,
+                            uint64_t ldgy, const float* lse_dev, uint64_t ldl, const float* bias_dev, uint64_t ldb, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed,
+                            uint64_t offset, uint16_t* gq_dev, uint64_t ldgq, uint16_t* gk_dev, uint64_t ldgk, uint16_t* gv_dev, uint64_t ldgv, float* gbias_dev, uint64_t ldgb) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_dropout16(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, bias_dev,
+                                                          ldb, heads, d, scale, drop_p, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, gbias_dev, ldgb, why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    HS_HIP(p, launch_bf16_drop_rows(p->rows.view, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, bias_dev, ldb, heads, d, scale, dr, gq_dev, ldgq, p->dsum.get(),
+                                      p->max_heads, p->stream));
+    HS_HIP(p, launch_bf16_drop_cols(p->cols.view, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, p->dsum.get(), p->max_heads, bias_dev, ldb, heads, d, scale, dr, gk_dev,
+                                      ldgk, gv_dev, ldgv, gbias_dev, ldgb, p->stream));
+    return HS_OK;
+}
+
+int hsmhd16_backward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* gy, const float* lse, const float* bias, uint32_t heads, uint32_t d,
+                     float scale, float drop_p, uint64_t seed, uint64_t offset, uint16_t* gq, uint16_t* gk, uint16_t* gv, float* gbias) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_dropout16_host(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz, q, k, v, gy, lse, bias, heads, d, scale, drop_p, gq, gk, gv, gbias,
+                                                               why))
+        return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const uint32_t w = heads * d;
+    Staging st(p);
+    const uint16_t* d_q = st.in(q, p->num_rows, w, w);
+    const uint16_t* d_k = st.in(k, p->num_cols, w, w);
+    const uint16_t* d_v = st.in(v, p->num_cols, w, w);
+    const uint16_t* d_gy = st.in(gy, p->num_rows, w, w);
+    const float* d_lse = st.in(lse, p->num_rows, heads, heads);
+    const float* d_b = st.in(bias, p->nnz, heads, heads);
+    uint16_t* d_gq = st.out(gq, p->num_rows, w, w);
+    uint16_t* d_gk = st.out(gk, p->num_cols, w, w);
+    uint16_t* d_gv = st.out(gv, p->num_cols, w, w);
+    float* d_gb = st.out(gbias, p->nnz, heads, heads);
+    return st.finish(st.failed() ? st.failed() : hsmhd16_backward_device(p, d_q, w, d_k, w, d_v, w, d_gy, w, d_lse, heads, d_b, heads, heads, d, scale, drop_p, seed, offset,
+                                                                        d_gq, w, d_gk, w, d_gv, w, d_gb, heads));
+}
 
 // ---- include/hisparse_gat.h: the same object, additive (GAT) scores from one word per node and head ---------------------------------------
 int hsgat_forward_device(hsmh_pattern* p, const float* el_dev, uint64_t ldel, const float* er_dev, uint64_t lder, const float* v_dev, uint64_t ldv, uint32_t heads, uint32_t d,

@@ -3,7 +3,7 @@
 // scale, the reach of an operand), hsab_common.h's overlap check of the backward and hsw_common.h's checks of one operand, all taken at
 // the width heads * d.  The calls with a bias of include/hisparse_heads_bias.h add the checks of their two per-entry arrays, and the
 // calls with dropout of include/hisparse_heads_dropout.h those of drop_p and of a bias that may be null, at the end, with hsmhd_keep_mask
-// itself, which both libraries export; the calls of include/hisparse_gat.h (additive scores from one word per node and head) their
+// itself, which both libraries export, and with the same over bf16 features for include/hisparse_heads_dropout_bf16.h; the calls of include/hisparse_gat.h (additive scores from one word per node and head) their
 // slope and the checks of the five head arrays, after that; the calls of include/hisparse_gatv2.h the checks of a, ga and the caller's
 // workspace, last.  Host code only.
 #ifndef HISPARSE_HSMH_COMMON_H_
@@ -14,6 +14,7 @@
 #include <string>
 
 #include "hisparse_heads.h"
+#include "hisparse_heads_dropout_bf16.h"
 #include "hsab_common.h"
 #include "philox.h"
 
@@ -413,6 +414,65 @@ inline int check_backward_dropout_host(uint32_t num_rows, uint32_t num_cols, uin
     if (int rc = check_backward_host(num_rows, num_cols, max_heads, true, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return rc;
     const uint64_t rb = uint64_t(num_rows) * heads * d * 4, cb = uint64_t(num_cols) * heads * d * 4, eb = nnz * heads * 4;
     const hsab::Range in[6] = {{"q", q, rb}, {"k", k, cb}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, uint64_t(num_rows) * heads * 4}, {"bias", nullptr, 0}};
+    const hsab::Range out[3] = {{"gq", gq, rb}, {"gk", gk, cb}, {"gv", gv, cb}};
+    if (int rc = check_bias_overlaps(in, out, gbias, eb, why)) return rc;
+    return check_drop(drop_p, why);
+}
+
+// ---- the bf16 calls with dropout of include/hisparse_heads_dropout_bf16.h: the bf16 rules for the features, the rules above for the rest --
+
+// hsmhd16_forward_device's arguments: hsmh16_forward_device's, bias (may be null) as one more input, and drop_p
+inline int check_forward_dropout16(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, uint64_t nnz, const uint16_t* q, uint64_t ldq, const uint16_t* k, uint64_t ldk,
+                                   const uint16_t* v, uint64_t ldv, const float* bias, uint64_t ldb, uint32_t heads, uint32_t d, float scale, float drop_p, const uint16_t* y,
+                                   uint64_t ldy, const float* lse, uint64_t ldl, std::string& why) {
+    if (int rc = check_forward16(num_rows, num_cols, max_heads, q, ldq, k, ldk, v, ldv, heads, d, scale, y, ldy, lse, ldl, why)) return rc;
+    if (bias) {
+        if (int rc = check_bias("bias", bias, ldb, heads, why)) return rc;
+        const uint64_t bb = bias_reach(nnz, ldb, heads);
+        if (int rc = check_apart("y", y, reach16(num_rows, ldy, heads * d), "bias", bias, bb, why)) return rc;
+        if (int rc = check_apart("lse", lse, lse_reach(num_rows, ldl, heads), "bias", bias, bb, why)) return rc;
+    }
+    return check_drop(drop_p, why);
+}
+
+// hsmhd16_forward's: ld = heads * d, ldl = ldb = heads, no alignment rule
+inline int check_forward_dropout16_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, uint64_t nnz, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                        const float* bias, uint32_t heads, uint32_t d, float scale, float drop_p, const uint16_t* y, const float* lse, std::string& why) {
+    if (int rc = check_forward16_host(num_rows, num_cols, max_heads, q, k, v, heads, d, scale, y, lse, why)) return rc;
+    const uint64_t bb = nnz * heads * 4;
+    if (int rc = check_apart("y", y, uint64_t(num_rows) * heads * d * 2, "bias", bias, bb, why)) return rc;
+    if (int rc = check_apart("lse", lse, uint64_t(num_rows) * heads * 4, "bias", bias, bb, why)) return rc;
+    return check_drop(drop_p, why);
+}
+
+// hsmhd16_backward_device's arguments: the map (it keys the column side's draws, with or without a bias), hsmh16_backward_device's, bias
+// (may be null) as one more input and gbias (may be null) as one more output
+inline int check_backward_dropout16(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool map, uint64_t nnz, const uint16_t* q, uint64_t ldq, const uint16_t* k, uint64_t ldk,
+                                    const uint16_t* v, uint64_t ldv, const uint16_t* gy, uint64_t ldgy, const float* lse, uint64_t ldl, const float* bias, uint64_t ldb, uint32_t heads,
+                                    uint32_t d, float scale, float drop_p, const uint16_t* gq, uint64_t ldgq, const uint16_t* gk, uint64_t ldgk, const uint16_t* gv, uint64_t ldgv,
+                                    const float* gbias, uint64_t ldgb, std::string& why) {
+    if (int rc = check_map(map, why, "dropout")) return rc;
+    if (int rc = check_backward16(num_rows, num_cols, max_heads, true, q, ldq, k, ldk, v, ldv, gy, ldgy, lse, ldl, heads, d, scale, gq, ldgq, gk, ldgk, gv, ldgv, why)) return rc;
+    if (bias)
+        if (int rc = check_bias("bias", bias, ldb, heads, why)) return rc;
+    if (gbias)
+        if (int rc = check_bias("gbias", gbias, ldgb, heads, why)) return rc;
+    const uint32_t w = heads * d;
+    const hsab::Range in[6] = {{"q", q, reach16(num_rows, ldq, w)}, {"k", k, reach16(num_cols, ldk, w)}, {"v", v, reach16(num_cols, ldv, w)},
+                               {"gy", gy, reach16(num_rows, ldgy, w)}, {"lse", lse, lse_reach(num_rows, ldl, heads)}, {"bias", bias, bias ? bias_reach(nnz, ldb, heads) : 0}};
+    const hsab::Range out[3] = {{"gq", gq, reach16(num_rows, ldgq, w)}, {"gk", gk, reach16(num_cols, ldgk, w)}, {"gv", gv, reach16(num_cols, ldgv, w)}};
+    if (int rc = check_bias_overlaps(in, out, gbias, gbias ? bias_reach(nnz, ldgb, heads) : 0, why)) return rc;
+    return check_drop(drop_p, why);
+}
+
+// hsmhd16_backward's: ld = heads * d, ldl = ldb = ldgb = heads, no alignment rule
+inline int check_backward_dropout16_host(uint32_t num_rows, uint32_t num_cols, uint32_t max_heads, bool map, uint64_t nnz, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                         const uint16_t* gy, const float* lse, const float* bias, uint32_t heads, uint32_t d, float scale, float drop_p, const uint16_t* gq,
+                                         const uint16_t* gk, const uint16_t* gv, const float* gbias, std::string& why) {
+    if (int rc = check_map(map, why, "dropout")) return rc;
+    if (int rc = check_backward16_host(num_rows, num_cols, max_heads, true, q, k, v, gy, lse, heads, d, scale, gq, gk, gv, why)) return rc;
+    const uint64_t rb = uint64_t(num_rows) * heads * d * 2, cb = uint64_t(num_cols) * heads * d * 2, eb = nnz * heads * 4;
+    const hsab::Range in[6] = {{"q", q, rb}, {"k", k, cb}, {"v", v, cb}, {"gy", gy, rb}, {"lse", lse, uint64_t(num_rows) * heads * 4}, {"bias", bias, bias ? eb : 0}};
     const hsab::Range out[3] = {{"gq", gq, rb}, {"gk", gk, cb}, {"gv", gv, cb}};
     if (int rc = check_bias_overlaps(in, out, gbias, eb, why)) return rc;
     return check_drop(drop_p, why);

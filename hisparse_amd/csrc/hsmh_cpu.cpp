@@ -16,6 +16,7 @@
 // The five hsmhd_* calls of include/hisparse_heads_dropout.h run the fp32 loops with a weight w = keep(e, h) ? c : 0 per entry and head from
 // philox.h's generator: forward, l over all entries and the sums over w times the weight; backward, GP becomes w GP and gV takes w P.
 // With drop_p = 0 every w is 1.0 and the loops form the words of the calls without dropout.
+// The four hsmhd16_* calls of include/hisparse_heads_dropout_bf16.h run those loops over bf16 elements: widen, the fp32 bias, w, narrow.
 // The four hsgat_* calls of include/hisparse_gat.h run loops of their own (gat_forward_head, gat_backward_head): the score is
 // x = el[row] + er[col], one fp32 add, and t = x > 0 ? x : slope * x, one fp32 multiply; the rest in double as above; gel = A - D B.
 // The six hsgat2_* calls of include/hisparse_gatv2.h run loops of their own too (gat2_forward_head, gat2_backward_head): z = xd + xs and
@@ -34,6 +35,7 @@
 #include "hisparse_heads_bf16.h"
 #include "hisparse_heads_bias.h"
 #include "hisparse_heads_dropout.h"
+#include "hisparse_heads_dropout_bf16.h"
 #include "hsmh_common.h"
 
 struct hsmh_pattern {
@@ -640,6 +642,58 @@ int hsmhd_backward(hsmh_pattern* p, const float* q, const float* k, const float*
 }
 
 int hsmhd_keep_mask(uint64_t nnz, uint32_t heads, float drop_p, uint64_t seed, uint64_t offset, uint8_t* keep) { return hisparse::hsmh::keep_mask(nnz, heads, drop_p, seed, offset, keep); }
+
+// ---- include/hisparse_heads_dropout_bf16.h: the same object, bf16 operands, dropout on the attention weights, a bias or none -------------
+int hsmhd16_forward_device(hsmh_pattern* p, const uint16_t* q_dev, uint64_t ldq, const uint16_t* k_dev, uint64_t ldk, const uint16_t* v_dev, uint64_t ldv, const float* bias_dev,
+                           uint64_t ldb, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed, uint64_t offset, uint16_t* y_dev, uint64_t ldy, float* lse_dev,
+                           uint64_t ldl) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_dropout16(p->num_rows, p->num_cols, p->max_heads, p->nnz(), q_dev, ldq, k_dev, ldk, v_dev, ldv, bias_dev, ldb, heads, d, scale, drop_p,
+                                                         y_dev, ldy, lse_dev, ldl, why))
+        return fail(p, rc, why);
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    forward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, heads, d, scale, y_dev, ldy, lse_dev, ldl, bias_dev, ldb, &dr);
+    return HS_OK;
+}
+
+int hsmhd16_forward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const uint16_t* v, const float* bias, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed,
+                    uint64_t offset, uint16_t* y, float* lse) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_forward_dropout16_host(p->num_rows, p->num_cols, p->max_heads, p->nnz(), q, k, v, bias, heads, d, scale, drop_p, y, lse, why))
+        return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    forward(p, q, w, k, w, v, w, heads, d, scale, y, w, lse, heads, bias, heads, &dr);
+    return HS_OK;
+}
+
+int hsmhd16_backward_device(hsmh_pattern* p, const uint16_t* q_dev, uint64_t ldq, const uint16_t* k_dev, uint64_t ldk, const uint16_t* v_dev, uint64_t ldv, const uint16_t* gy_dev,
+                            uint64_t ldgy, const float* lse_dev, uint64_t ldl, const float* bias_dev, uint64_t ldb, uint32_t heads, uint32_t d, float scale, float drop_p, uint64_t seed,
+                            uint64_t offset, uint16_t* gq_dev, uint64_t ldgq, uint16_t* gk_dev, uint64_t ldgk, uint16_t* gv_dev, uint64_t ldgv, float* gbias_dev, uint64_t ldgb) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_dropout16(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz(), q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl,
+                                                          bias_dev, ldb, heads, d, scale, drop_p, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, gbias_dev, ldgb, why))
+        return fail(p, rc, why);
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    backward(p, q_dev, ldq, k_dev, ldk, v_dev, ldv, gy_dev, ldgy, lse_dev, ldl, heads, d, scale, gq_dev, ldgq, gk_dev, ldgk, gv_dev, ldgv, bias_dev, ldb, gbias_dev, ldgb, &dr);
+    return HS_OK;
+}
+
+int hsmhd16_backward(hsmh_pattern* p, const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* gy, const float* lse, const float* bias, uint32_t heads, uint32_t d,
+                     float scale, float drop_p, uint64_t seed, uint64_t offset, uint16_t* gq, uint16_t* gk, uint16_t* gv, float* gbias) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsmh::check_backward_dropout16_host(p->num_rows, p->num_cols, p->max_heads, p->map, p->nnz(), q, k, v, gy, lse, bias, heads, d, scale, drop_p, gq, gk, gv,
+                                                               gbias, why))
+        return fail(p, rc, why);
+    const uint64_t w = uint64_t(heads) * d;
+    const hisparse::philox::Dropout dr = hisparse::philox::dropout_of(drop_p, seed, offset);
+    backward(p, q, w, k, w, v, w, gy, w, lse, heads, heads, d, scale, gq, w, gk, w, gv, w, bias, heads, gbias, heads, &dr);
+    return HS_OK;
+}
 
 // ---- include/hisparse_gat.h: the same object, additive (GAT) scores from one word per node and head ----------------------------------
 int hsgat_forward_device(hsmh_pattern* p, const float* el_dev, uint64_t ldel, const float* er_dev, uint64_t lder, const float* v_dev, uint64_t ldv, uint32_t heads, uint32_t d,

@@ -1,6 +1,6 @@
 // wide_lanes.h — the device side of wide_products.h's schedule, defined ONCE for every kernel that runs on it: wide_products.hip,
 // pattern_attention.hip, attention_backward.hip, heads_attention.hip, heads16_attention.hip, heads_bias_attention.hip,
-// heads_dropout_attention.hip, gat_attention.hip and gatv2_attention.hip.  Only .hip files include it.  wide_products.h owns the table, the side and the
+// heads_dropout_attention.hip, heads16_dropout_attention.hip, gat_attention.hip and gatv2_attention.hip.  Only .hip files include it.  wide_products.h owns the table, the side and the
 // constants; this header owns what a lane does with them:
 //   which virtual workgroup gets which row (class_of, Work, pick) and how many trips a wavefront makes so that its shuffles stay
 //     convergent (trips_of);
@@ -11,8 +11,8 @@
 // The kernels that share these are compared bit for bit by the tests (zero bias against the plain calls, drop_p = 0 against both), so
 // the order of every sum below is part of the contract.  A change here reaches every file above: tools/device_asm_digest.py shows
 // which kernels' code it moved.  Everything is __forceinline__ and leaves no symbol in a code object.
-// A kernel file pulls in what it uses, `using namespace lanes;` where nothing clashes; heads16_attention.hip keeps an eight-sum State under
-// the same name and names what it takes.  The two oldest files still write pick and trips_of out in a kernel body (pattern_attention_kernel,
+// A kernel file pulls in what it uses, `using namespace lanes;` where nothing clashes; heads16_attention.hip and
+// heads16_dropout_attention.hip keep an eight-sum State under the same name and name what they take.  The two oldest files still write pick and trips_of out in a kernel body (pattern_attention_kernel,
 // wide_dot_kernel; wide_gather_kernel has team_row): with the calls they compile to other code, and the header was brought in without
 // moving any.  A fix to pick has those three places to visit besides this one.
 #ifndef HISPARSE_WIDE_LANES_H_

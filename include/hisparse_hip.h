@@ -309,6 +309,7 @@ int hs_load_matrix_csr_transposed(hs_context* ctx, uint32_t num_rows, uint32_t n
  * hisparse_heads_bf16.h adds the same two steps over bf16 operands to that object, and hisparse_heads_bias.h the same two steps with a
  * per-entry, per-head additive bias on the score and the gradient of that bias, and hisparse_heads_dropout.h the same two steps with
  * dropout on the attention weights, the mask recomputed from a counter-based generator in both directions and never stored, and
+ * hisparse_heads_dropout_bf16.h those two steps with the bias and the dropout over bf16 operands, and
  * hisparse_gat.h the graph attention (GAT) step on that object: additive scores from one word per node and head, forward and backward, and
  * hisparse_gatv2.h the GATv2 step: the score a . LeakyReLU(XD[row] + XS[col]) and the gradient of a.) */
 int hs_update_values(hs_context* ctx, const float* values, uint64_t nnz);
