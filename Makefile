@@ -13,7 +13,7 @@ CXXFLAGS  := -O3 -std=c++17 -fPIC -Wall -Wextra -pthread $(INC)
 HIPFLAGS  := -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -ffp-contract=off -Wall $(INC)
 
 HOST_HDRS := $(wildcard include/hisparse/*.h) include/hisparse_host.h
-HIP_HDRS  := include/hisparse_hip.h include/hisparse_pattern.h include/hisparse_rows.h include/hisparse_wide.h include/hisparse_attention.h include/hisparse_attention_backward.h include/hisparse_heads.h include/hisparse_heads_bf16.h include/hisparse_heads_bias.h include/hisparse_heads_dropout.h include/hisparse_heads_dropout_bf16.h include/hisparse_gat.h include/hisparse_gatv2.h $(wildcard $(CSRC)/*.h) include/hisparse/common.h
+HIP_HDRS  := include/hisparse_hip.h include/hisparse_pattern.h include/hisparse_rows.h include/hisparse_wide.h include/hisparse_attention.h include/hisparse_attention_backward.h include/hisparse_heads.h include/hisparse_heads_bf16.h include/hisparse_heads_bias.h include/hisparse_heads_dropout.h include/hisparse_heads_dropout_bf16.h include/hisparse_gat.h include/hisparse_gatv2.h include/hisparse_aggregate.h $(wildcard $(CSRC)/*.h) include/hisparse/common.h
 
 .PHONY: all host hip cpu oracle benchmark clean prof variant
 all: host hip cpu oracle benchmark
@@ -32,7 +32,7 @@ $(LIBDIR)/libhisparse_host.so: $(CSRC)/host_capi.cpp $(HOST_HDRS) | $(LIBDIR)
 
 # One object per translation unit (an edit of one kernel file recompiles that file only); objects live in build/ (git-ignored, and listed in
 # .gpurunignore: the GPU box needs the libraries, not the objects).
-HIP_UNITS := hs_api.cpp hs_load.cpp hs_spmspv.cpp hs_spmm.cpp tiles_capi.cpp stream_tiles.cpp bitmap_tiles.cpp sweep_tiles.cpp spmv_kernels.hip spmv_bitmap.hip spmv_sweep.hip spmspv.hip spmm_bitmap.hip spmm_mfma.hip spmm_sweep.hip gpu_tiles.hip value_update.hip hsp_api.cpp sddmm.hip hsr_api.cpp row_softmax.hip hsw_api.cpp wide_products.hip hsat_api.cpp pattern_attention.hip hsab_api.cpp attention_backward.hip hsmh_api.cpp heads_attention.hip heads16_attention.hip heads_bias_attention.hip heads_dropout_attention.hip heads16_dropout_attention.hip gat_attention.hip gatv2_attention.hip
+HIP_UNITS := hs_api.cpp hs_load.cpp hs_spmspv.cpp hs_spmm.cpp tiles_capi.cpp stream_tiles.cpp bitmap_tiles.cpp sweep_tiles.cpp spmv_kernels.hip spmv_bitmap.hip spmv_sweep.hip spmspv.hip spmm_bitmap.hip spmm_mfma.hip spmm_sweep.hip gpu_tiles.hip value_update.hip hsp_api.cpp sddmm.hip hsr_api.cpp row_softmax.hip hsw_api.cpp wide_products.hip hsat_api.cpp pattern_attention.hip hsab_api.cpp attention_backward.hip hsmh_api.cpp heads_attention.hip heads16_attention.hip heads_bias_attention.hip heads_dropout_attention.hip heads16_dropout_attention.hip gat_attention.hip gatv2_attention.hip neighbor_aggregate.hip
 OBJDIR    := $(ROOT)/build
 HIP_OBJS  := $(addprefix $(OBJDIR)/prod/,$(addsuffix .o,$(HIP_UNITS)))
 PROF_OBJS := $(addprefix $(OBJDIR)/prof/,$(addsuffix .o,$(HIP_UNITS)))
@@ -68,7 +68,7 @@ endif
 
 # the same C-ABI on host threads for machines without a GPU: a separate library a driver links INSTEAD (never a fallback of the HIP one)
 # (hsp_cpu.cpp: include/hisparse_pattern.h on the host, the twin of hsp_api.cpp + sddmm.hip; hsr_cpu.cpp: include/hisparse_rows.h, the twin
-# of hsr_api.cpp + row_softmax.hip; hsw_cpu.cpp: include/hisparse_wide.h, the twin of hsw_api.cpp + wide_products.hip; hsat_cpu.cpp: include/hisparse_attention.h, the twin of
+# of hsr_api.cpp + row_softmax.hip; hsw_cpu.cpp: include/hisparse_wide.h and include/hisparse_aggregate.h, the twin of hsw_api.cpp + wide_products.hip + neighbor_aggregate.hip; hsat_cpu.cpp: include/hisparse_attention.h, the twin of
 # hsat_api.cpp + pattern_attention.hip; hsab_cpu.cpp: include/hisparse_attention_backward.h, the twin of hsab_api.cpp + attention_backward.hip;
 # hsmh_cpu.cpp: include/hisparse_heads.h, include/hisparse_heads_bf16.h, include/hisparse_heads_bias.h, include/hisparse_heads_dropout.h, include/hisparse_heads_dropout_bf16.h and
 # include/hisparse_gat.h and include/hisparse_gatv2.h, the twin of hsmh_api.cpp + heads_attention.hip + heads16_attention.hip + heads_bias_attention.hip + heads_dropout_attention.hip + heads16_dropout_attention.hip +

@@ -14,6 +14,7 @@ Layout:
   heads16_dropout.py ctypes face of include/hisparse_heads_dropout_bf16.h (that bias and dropout over bf16 operands)
   gat.py       ctypes face of include/hisparse_gat.h (the same object with GAT's additive scores, el[row] + er[col] through a LeakyReLU)
   gatv2.py     ctypes face of include/hisparse_gatv2.h (the same object with GATv2's score, a . LeakyReLU(XD[row] + XS[col]), and the gradient of a)
+  aggregate.py ctypes face of include/hisparse_aggregate.h (sum, mean, max and min of the neighbours' rows on wide.py's object, with the arg-based backward)
   datasets.py  the reference's benchmark matrices as seeded stand-ins
   sharding.py  row-block sharding of one matrix across the GPUs of a node (+ RCCL gather of y)
   csrc/        C++ / HIP sources of the two libraries and the `benchmark` driver
@@ -32,5 +33,6 @@ from . import heads_dropout  # noqa: F401
 from . import heads16_dropout  # noqa: F401
 from . import gat  # noqa: F401
 from . import gatv2  # noqa: F401
+from . import aggregate  # noqa: F401
 
-__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads", "heads16", "heads_bias", "heads_dropout", "heads16_dropout", "gat", "gatv2"]
+__all__ = ["host", "device", "datasets", "rows", "wide", "attention", "attention_backward", "heads", "heads16", "heads_bias", "heads_dropout", "heads16_dropout", "gat", "gatv2", "aggregate"]

@@ -4,11 +4,14 @@
 // the map from its entries back to CSR order.  Both schedules and the transposed pattern are built on the host (wide_schedule.h, which
 // also uploads a side; hsw_common.h); the kernels are in wide_products.hip; what the object shares with the other pattern objects, and
 // the host forms' transient buffers, are pattern_object.h's.  Nothing here touches a context, an hsp_pattern or a numeric mode.
+// The four calls of include/hisparse_aggregate.h (hsagg_*: sum, mean, max and min of the neighbours' rows, and their backward) work on
+// the same object and are at the end of this file; their kernels are in neighbor_aggregate.hip.
 #include <new>
 #include <string>
 #include <vector>
 
 #include "hsw_common.h"
+#include "neighbor_aggregate.h"
 #include "wide_products.h"
 #include "wide_schedule.h"
 
@@ -47,6 +50,16 @@ int spmm_host(hsw_pattern* p, bool transposed, const float* w, const float* x, u
     const float* d_x = st.in(x, x_rows, d, ld);
     float* d_y = st.out(y, y_rows, d, ld);
     return st.finish(st.failed() ? st.failed() : transposed ? hsw_spmm_t_device(p, d_w, d_x, ld, d, d_y, ld) : hsw_spmm_device(p, d_w, d_x, ld, d, d_y, ld));
+}
+
+// the bits of a checked `ops` word (hisparse_aggregate.h) as the launchers take them
+AggregateOps aggregators(uint32_t ops) {
+    AggregateOps a;
+    a.sum = (ops & HSAGG_SUM) != 0;
+    a.mean = (ops & HSAGG_MEAN) != 0;
+    a.max = (ops & HSAGG_MAX) != 0;
+    a.min = (ops & HSAGG_MIN) != 0;
+    return a;
 }
 
 }  // namespace
@@ -127,6 +140,63 @@ int hsw_spmm_t(hsw_pattern* p, const float* w, const float* x, uint32_t d, float
     if (!p) return HS_ERR_BAD_ARG;
     if (!p->transposed) return fail(p, HS_ERR_UNSUPPORTED, "the object was created without HSW_TRANSPOSED");
     return spmm_host(p, true, w, x, d, y);
+}
+
+// ---- include/hisparse_aggregate.h: sum / mean / max / min of the neighbours' rows, on the same object ------------------------------------
+int hsagg_forward_device(hsw_pattern* p, uint32_t ops, const float* x_dev, uint64_t ldx, uint32_t d, float* ysum_dev, float* ymax_dev, uint32_t* amax_dev, float* ymin_dev,
+                         uint32_t* amin_dev, uint64_t ldy) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsw::check_agg_forward(p->num_rows, p->num_cols, ops, x_dev, ldx, d, ysum_dev, ymax_dev, amax_dev, ymin_dev, amin_dev, ldy, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HS_HIP(p, launch_neighbor_forward(p->rows.view, aggregators(ops), x_dev, ldx, d, ysum_dev, ymax_dev, amax_dev, ymin_dev, amin_dev, ldy, p->stream));
+    return HS_OK;
+}
+
+int hsagg_backward_device(hsw_pattern* p, uint32_t ops, const float* gsum_dev, const float* gmax_dev, const uint32_t* amax_dev, const float* gmin_dev, const uint32_t* amin_dev,
+                          uint64_t ldg, uint32_t d, float* gx_dev, uint64_t ldgx) {
+    if (!p) return HS_ERR_BAD_ARG;
+    if (!p->transposed) return fail(p, HS_ERR_UNSUPPORTED, "the object was created without HSW_TRANSPOSED");
+    std::string why;
+    if (int rc = hisparse::hsw::check_agg_backward(p->num_rows, p->num_cols, ops, gsum_dev, gmax_dev, amax_dev, gmin_dev, amin_dev, ldg, d, gx_dev, ldgx, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    HS_HIP(p, launch_neighbor_backward(p->cols.view, p->rows.view.ptr, aggregators(ops), gsum_dev, gmax_dev, amax_dev, gmin_dev, amin_dev, ldg, d, gx_dev, ldgx, p->stream));
+    return HS_OK;
+}
+
+int hsagg_forward(hsw_pattern* p, uint32_t ops, const float* x, uint32_t d, float* ysum, float* ymax, uint32_t* amax, float* ymin, uint32_t* amin) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsw::check_agg_forward_host(p->num_rows, p->num_cols, ops, x, d, ysum, ymax, amax, ymin, amin, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const AggregateOps a = aggregators(ops);
+    const uint64_t ld = hisparse::hsp::round_up4(d);
+    Staging st(p);      // an output the call does not write is left out: a null host pointer is a null device pointer and no memory
+    const float* d_x = st.in(x, p->num_cols, d, ld);
+    float* d_sum = st.out(a.sum || a.mean ? ysum : nullptr, p->num_rows, d, ld);
+    float* d_max = st.out(a.max ? ymax : nullptr, p->num_rows, d, ld);
+    uint32_t* d_amax = st.out(a.max ? amax : nullptr, p->num_rows, d, ld);
+    float* d_min = st.out(a.min ? ymin : nullptr, p->num_rows, d, ld);
+    uint32_t* d_amin = st.out(a.min ? amin : nullptr, p->num_rows, d, ld);
+    return st.finish(st.failed() ? st.failed() : hsagg_forward_device(p, ops, d_x, ld, d, d_sum, d_max, d_amax, d_min, d_amin, ld));
+}
+
+int hsagg_backward(hsw_pattern* p, uint32_t ops, const float* gsum, const float* gmax, const uint32_t* amax, const float* gmin, const uint32_t* amin, uint32_t d, float* gx) {
+    if (!p) return HS_ERR_BAD_ARG;
+    if (!p->transposed) return fail(p, HS_ERR_UNSUPPORTED, "the object was created without HSW_TRANSPOSED");
+    std::string why;
+    if (int rc = hisparse::hsw::check_agg_backward_host(p->num_rows, p->num_cols, ops, gsum, gmax, amax, gmin, amin, d, gx, why)) return fail(p, rc, why);
+    if (int rc = enter(p)) return rc;
+    const AggregateOps a = aggregators(ops);
+    const uint64_t ld = hisparse::hsp::round_up4(d);
+    Staging st(p);
+    const float* d_sum = st.in(a.sum || a.mean ? gsum : nullptr, p->num_rows, d, ld);
+    const float* d_max = st.in(a.max ? gmax : nullptr, p->num_rows, d, ld);
+    const uint32_t* d_amax = st.in(a.max ? amax : nullptr, p->num_rows, d, ld);
+    const float* d_min = st.in(a.min ? gmin : nullptr, p->num_rows, d, ld);
+    const uint32_t* d_amin = st.in(a.min ? amin : nullptr, p->num_rows, d, ld);
+    float* d_gx = st.out(gx, p->num_cols, d, ld);
+    return st.finish(st.failed() ? st.failed() : hsagg_backward_device(p, ops, d_sum, d_max, d_amax, d_min, d_amin, ld, d, d_gx, ld));
 }
 
 }  // extern "C"

@@ -6,7 +6,11 @@
 // Arithmetic = the kernels' (wide_products.hip), the header's ARITHMETIC block: one fp32 multiply per product (built with
 // -ffp-contract=off), the products of an output word added in double from +0.0, one rounding.  The transposed pattern is the one the HIP
 // library builds (hsw_common.h): a column's entries in ascending CSR index.
+// The four calls of include/hisparse_aggregate.h (the twin of neighbor_aggregate.hip) are here too, on the same object: the winner rule is
+// written as the header defines it, a walk over the row's entries, not as the kernels merge.
 // No dependency beyond the headers and hsw_common.h: tests/cpp/test_wide_cpu.cpp compiles this file alone under the sanitizers.
+#include <cmath>
+#include <cstring>
 #include <new>
 #include <string>
 #include <vector>
@@ -55,6 +59,75 @@ void spmm(uint32_t rows, const uint32_t* ptr, const uint32_t* idx, const uint32_
         }
         float* dst = y + uint64_t(r) * ldy;
         for (uint32_t j = 0; j < d; ++j) dst[j] = float(s[j]);
+    }
+}
+
+// ---- include/hisparse_aggregate.h ---------------------------------------------------------------------------------------------------------
+// the rank of the header's winner rule: v outranks b when it is a NaN against a non-NaN, else when the IEEE comparison says so; words
+// that are equal (== or both NaN) do not outrank each other, and the smaller index then wins
+bool outranks(float v, float b, bool max) {
+    if (std::isnan(v) != std::isnan(b)) return std::isnan(v);
+    if (std::isnan(v)) return false;
+    return max ? v > b : v < b;
+}
+
+// the CSR index of the winner of feature j among row r's entries, HSAGG_NONE for a row without entries: the entries are walked in
+// ascending index and only a word that outranks the best so far replaces it, so among equals the smallest index stays
+uint32_t winner(const hsw_pattern* p, uint32_t r, const float* x, uint64_t ldx, uint32_t j, bool max) {
+    uint32_t best = HSAGG_NONE;
+    for (uint32_t e = p->indptr[r]; e < p->indptr[r + 1]; ++e)
+        if (best == HSAGG_NONE || outranks(x[uint64_t(p->indices[e]) * ldx + j], x[uint64_t(p->indices[best]) * ldx + j], max)) best = e;
+    return best;
+}
+
+// an extreme's word: the winner's word of X as it is, +0.0f for a row without entries
+void copy_word(float* dst, const hsw_pattern* p, uint32_t e, const float* x, uint64_t ldx, uint32_t j) {
+    const float zero = 0.0f;
+    std::memcpy(dst, e == HSAGG_NONE ? &zero : &x[uint64_t(p->indices[e]) * ldx + j], sizeof(float));
+}
+
+void aggregate(const hsw_pattern* p, uint32_t ops, const float* x, uint64_t ldx, uint32_t d, float* ysum, float* ymax, uint32_t* amax, float* ymin, uint32_t* amin, uint64_t ldy) {
+    for (uint32_t r = 0; r < p->num_rows; ++r) {
+        const uint32_t lo = p->indptr[r], hi = p->indptr[r + 1];
+        for (uint32_t j = 0; j < d; ++j) {
+            const uint64_t at = uint64_t(r) * ldy + j;
+            if (ops & (HSAGG_SUM | HSAGG_MEAN)) {
+                double s = 0.0;
+                for (uint32_t e = lo; e < hi; ++e) s += double(x[uint64_t(p->indices[e]) * ldx + j]);
+                if ((ops & HSAGG_MEAN) && hi > lo) s /= double(hi - lo);
+                ysum[at] = float(s);
+            }
+            if (ops & HSAGG_MAX) {
+                const uint32_t e = winner(p, r, x, ldx, j, true);
+                copy_word(ymax + at, p, e, x, ldx, j);
+                if (amax) amax[at] = e;
+            }
+            if (ops & HSAGG_MIN) {
+                const uint32_t e = winner(p, r, x, ldx, j, false);
+                copy_word(ymin + at, p, e, x, ldx, j);
+                if (amin) amin[at] = e;
+            }
+        }
+    }
+}
+
+// gx[c][j]: over the entries k of column c, the gradient words of row(k) -- the sum's (the mean's: over the row's length, one double
+// division) and an extreme's where the row's arg word names k's CSR index
+void aggregate_backward(const hsw_pattern* p, uint32_t ops, const float* gsum, const float* gmax, const uint32_t* amax, const float* gmin, const uint32_t* amin, uint64_t ldg,
+                        uint32_t d, float* gx, uint64_t ldgx) {
+    for (uint32_t c = 0; c < p->num_cols; ++c) {
+        for (uint32_t j = 0; j < d; ++j) {
+            double s = 0.0;
+            for (uint32_t k = p->cptr[c]; k < p->cptr[c + 1]; ++k) {
+                const uint32_t r = p->trow[k], e = p->perm[k];
+                const uint64_t at = uint64_t(r) * ldg + j;
+                if (ops & HSAGG_SUM) s += double(gsum[at]);
+                if (ops & HSAGG_MEAN) s += double(gsum[at]) / double(p->indptr[r + 1] - p->indptr[r]);
+                if ((ops & HSAGG_MAX) && amax[at] == e) s += double(gmax[at]);
+                if ((ops & HSAGG_MIN) && amin[at] == e) s += double(gmin[at]);
+            }
+            gx[uint64_t(c) * ldgx + j] = float(s);
+        }
     }
 }
 
@@ -149,6 +222,42 @@ int hsw_spmm_t(hsw_pattern* p, const float* w, const float* x, uint32_t d, float
     std::string why;
     if (int rc = hisparse::hsw::check_host(d, w, p->nnz(), x, uint64_t(p->num_rows) * d, y, uint64_t(p->num_cols) * d, why)) return fail(p, rc, why);
     spmm(p->num_cols, p->cptr.data(), p->trow.data(), p->perm.data(), w, x, d, d, y, d);
+    return HS_OK;
+}
+
+int hsagg_forward_device(hsw_pattern* p, uint32_t ops, const float* x_dev, uint64_t ldx, uint32_t d, float* ysum_dev, float* ymax_dev, uint32_t* amax_dev, float* ymin_dev,
+                         uint32_t* amin_dev, uint64_t ldy) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsw::check_agg_forward(p->num_rows, p->num_cols, ops, x_dev, ldx, d, ysum_dev, ymax_dev, amax_dev, ymin_dev, amin_dev, ldy, why)) return fail(p, rc, why);
+    aggregate(p, ops, x_dev, ldx, d, ysum_dev, ymax_dev, amax_dev, ymin_dev, amin_dev, ldy);
+    return HS_OK;
+}
+
+int hsagg_backward_device(hsw_pattern* p, uint32_t ops, const float* gsum_dev, const float* gmax_dev, const uint32_t* amax_dev, const float* gmin_dev, const uint32_t* amin_dev,
+                          uint64_t ldg, uint32_t d, float* gx_dev, uint64_t ldgx) {
+    if (!p) return HS_ERR_BAD_ARG;
+    if (!p->transposed) return fail(p, HS_ERR_UNSUPPORTED, "the object was created without HSW_TRANSPOSED");
+    std::string why;
+    if (int rc = hisparse::hsw::check_agg_backward(p->num_rows, p->num_cols, ops, gsum_dev, gmax_dev, amax_dev, gmin_dev, amin_dev, ldg, d, gx_dev, ldgx, why)) return fail(p, rc, why);
+    aggregate_backward(p, ops, gsum_dev, gmax_dev, amax_dev, gmin_dev, amin_dev, ldg, d, gx_dev, ldgx);
+    return HS_OK;
+}
+
+int hsagg_forward(hsw_pattern* p, uint32_t ops, const float* x, uint32_t d, float* ysum, float* ymax, uint32_t* amax, float* ymin, uint32_t* amin) {
+    if (!p) return HS_ERR_BAD_ARG;
+    std::string why;
+    if (int rc = hisparse::hsw::check_agg_forward_host(p->num_rows, p->num_cols, ops, x, d, ysum, ymax, amax, ymin, amin, why)) return fail(p, rc, why);
+    aggregate(p, ops, x, d, d, ysum, ymax, amax, ymin, amin, d);
+    return HS_OK;
+}
+
+int hsagg_backward(hsw_pattern* p, uint32_t ops, const float* gsum, const float* gmax, const uint32_t* amax, const float* gmin, const uint32_t* amin, uint32_t d, float* gx) {
+    if (!p) return HS_ERR_BAD_ARG;
+    if (!p->transposed) return fail(p, HS_ERR_UNSUPPORTED, "the object was created without HSW_TRANSPOSED");
+    std::string why;
+    if (int rc = hisparse::hsw::check_agg_backward_host(p->num_rows, p->num_cols, ops, gsum, gmax, amax, gmin, amin, d, gx, why)) return fail(p, rc, why);
+    aggregate_backward(p, ops, gsum, gmax, amax, gmin, amin, d, d, gx, d);
     return HS_OK;
 }
 

@@ -1,12 +1,13 @@
 // wide_lanes.h — the device side of wide_products.h's schedule, defined ONCE for every kernel that runs on it: wide_products.hip,
 // pattern_attention.hip, attention_backward.hip, heads_attention.hip, heads16_attention.hip, heads_bias_attention.hip,
-// heads_dropout_attention.hip, heads16_dropout_attention.hip, gat_attention.hip and gatv2_attention.hip.  Only .hip files include it.  wide_products.h owns the table, the side and the
+// heads_dropout_attention.hip, heads16_dropout_attention.hip, gat_attention.hip, gatv2_attention.hip and neighbor_aggregate.hip.  Only .hip files include it.  wide_products.h owns the table, the side and the
 // constants; this header owns what a lane does with them:
 //   which virtual workgroup gets which row (class_of, Work, pick) and how many trips a wavefront makes so that its shuffles stay
 //     convergent (trips_of);
 //   a lane's place in its group when a feature row holds several heads (Place, place_of);
 //   how the groups of a team and the four wavefronts of a long row merge (merge_lanes, merge_waves; State, raise_to, merge_states for
-//     the online softmax of the forward kernels);
+//     the online softmax of the forward kernels; Best4, outranks, merge_best_lanes, merge_best_waves for the (value, index) pairs of
+//     the neighbour aggregation's extremes);
 //   the small words around them (f32x4, Sum4, dot4, store4, pick4, lse_of), and for the launchers grid_of and shape_ok.
 // The kernels that share these are compared bit for bit by the tests (zero bias against the plain calls, drop_p = 0 against both), so
 // the order of every sum below is part of the contract.  A change here reaches every file above: tools/device_asm_digest.py shows
@@ -190,6 +191,68 @@ __device__ __forceinline__ void merge_waves(double (&red)[kWaves][kN][64], doubl
     if (wave == 0 && lane < group) {
 #pragma unroll
         for (uint32_t j = 0; j < kN; ++j) acc[j] = ((red[0][j][lane] + red[1][j][lane]) + red[2][j][lane]) + red[3][j][lane];
+    }
+}
+
+// ---- (value, index) pairs across a team and across the wavefronts of a long row: the extremes of neighbor_aggregate.hip ---------------------
+// the four candidates of a lane's chunk: v[j] is a word of X as it was loaded (never the result of arithmetic), e[j] the CSR index of its
+// entry.  An empty candidate is (-inf, ~0u) for the maximum and (+inf, ~0u) for the minimum: every entry outranks it, an entry of the
+// same value by its smaller index.
+struct Best4 {
+    float v[4];
+    uint32_t e[4];
+};
+
+// include/hisparse_aggregate.h's winner rule: (v, e) is taken over (bv, be) when it is a NaN against a non-NaN, else when the IEEE
+// comparison says so (fmaxf and v_max_f32 would DROP the NaN), else, among equals (== or both NaN), when its index is the smaller.  A
+// lexicographic order on (rank, e), total on the entries of a row: folding candidates in any order and any grouping gives one winner.
+template <bool kMax>
+__device__ __forceinline__ bool outranks(float v, uint32_t e, float bv, uint32_t be) {
+    const bool vn = v != v, bn = bv != bv;
+    const bool better = (kMax ? v > bv : v < bv) || (vn && !bn);
+    const bool equal = v == bv || (vn && bn);
+    return better || (equal && e < be);
+}
+
+template <bool kMax>
+__device__ __forceinline__ void offer(Best4& b, uint32_t j, float v, uint32_t e) {
+    if (outranks<kMax>(v, e, b.v[j], b.e[j])) {
+        b.v[j] = v;
+        b.e[j] = e;
+    }
+}
+
+// the pairs of the lanes that differ in the bits from ... to/2 of the lane index become one: every such lane ends with the winner
+template <bool kMax>
+__device__ __forceinline__ void merge_best_lanes(Best4& b, uint32_t from, uint32_t to) {
+    for (uint32_t k = from; k < to; k <<= 1) {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const float v = __shfl_xor(b.v[j], int(k), 64);
+            const uint32_t e = uint32_t(__shfl_xor(int(b.e[j]), int(k), 64));
+            offer<kMax>(b, j, v, e);
+        }
+    }
+}
+
+// a long row: the four wavefronts' pairs through LDS into wave 0's lanes < group (the others' are left as they were); the caller syncs
+// once more before the next use of the two arrays
+template <bool kMax>
+__device__ __forceinline__ void merge_best_waves(float (&red_v)[kWaves][4][64], uint32_t (&red_e)[kWaves][4][64], Best4& b, uint32_t lane, uint32_t wave, uint32_t group) {
+    if (lane < group) {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            red_v[wave][j][lane] = b.v[j];
+            red_e[wave][j][lane] = b.e[j];
+        }
+    }
+    __syncthreads();
+    if (wave == 0 && lane < group) {
+#pragma unroll
+        for (uint32_t w = 1; w < kWaves; ++w) {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) offer<kMax>(b, j, red_v[w][j][lane], red_e[w][j][lane]);
+        }
     }
 }
 

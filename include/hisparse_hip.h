@@ -311,7 +311,9 @@ int hs_load_matrix_csr_transposed(hs_context* ctx, uint32_t num_rows, uint32_t n
  * dropout on the attention weights, the mask recomputed from a counter-based generator in both directions and never stored, and
  * hisparse_heads_dropout_bf16.h those two steps with the bias and the dropout over bf16 operands, and
  * hisparse_gat.h the graph attention (GAT) step on that object: additive scores from one word per node and head, forward and backward, and
- * hisparse_gatv2.h the GATv2 step: the score a . LeakyReLU(XD[row] + XS[col]) and the gradient of a.) */
+ * hisparse_gatv2.h the GATv2 step: the score a . LeakyReLU(XD[row] + XS[col]) and the gradient of a; hisparse_aggregate.h adds to
+ * hisparse_wide.h's object the aggregations that are not weighted sums: sum, mean, max and min of the neighbours' rows in one launch, and
+ * the backward that sends a gradient to the winning source.) */
 int hs_update_values(hs_context* ctx, const float* values, uint64_t nnz);
 int hs_update_values_device(hs_context* ctx, const float* values_dev, uint64_t nnz);
 
